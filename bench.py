@@ -11,6 +11,15 @@ Workload = BASELINE.json configs[2]; scaling is weak (16384 envs per GPU).
 
 Rank 0 prints ONE JSON line.  value = all env-steps processed by all ranks
 (N_total * T * K) / max-over-ranks wall time of the K timed iterations.
+
+A plain run sets up, warms up, times the K iterations and prints the headline
+line (value, ms_per_step, the workload and the rollout / GAE / update split of
+the timed iterations).  `--dump-outputs DIR` also writes what the last timed
+iteration computed as DIR/<name>.npy.  `--full` adds every measurement that
+takes runs of its own after the timed region: the rooflines (live kernel
+spans, marginal and event-bracketed timings, the committed rocprof figures
+beside them), the env / rollout sweeps, propagators, reachable domain,
+surrogate, the data-parallel measurements at N > 1 and the CPU baselines.
 """
 import argparse
 import json
@@ -49,6 +58,15 @@ def parse():
     ap.add_argument("--minibatch", type=int, default=4096)
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--d-capture", type=float, default=15000.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed iterations also run every other measurement (rooflines, sweeps, "
+                         "propagators, reachable domain, surrogate, data-parallel figures, CPU baselines) and "
+                         "report them in the line (--cpu-baseline-seconds, --no-cpu-baseline, --kernel-iters, "
+                         "--profile-tag and --global-slice only matter here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed iteration computed (rank 0's shard) as DIR/<name>.npy: the "
+                         "learner's updated parameters, the env statistics it returned, and a fixed seeded sample "
+                         "of the rollout table (obs, act, logp, rew, done, values, adv, vtarget)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=6.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-iters", type=int, default=200)
@@ -411,6 +429,74 @@ def run(a, world):
     n_total = a.num_envs * n_gpus
     env_steps = n_total * a.horizon * a.steps
     value = env_steps / elapsed
+    rollout_ms = sum(timers["rollout_ms"]) / len(timers["rollout_ms"])
+    update_ms = sum(timers["update_ms"]) / len(timers["update_ms"])
+    gae_ms = sum(timers["gae_ms"]) / len(timers["gae_ms"])
+    n_minibatches = a.epochs * ((a.num_envs * a.horizon) // tr.mb_local)
+    line = {
+        "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": n_gpus, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64+f32",
+        "data": "synthetic: reference reset state, random-init (orthogonal, seed 0) policies",
+        "config": {"workload": workload_name(a, n_gpus),
+                   "num_envs_per_gpu": a.num_envs, "num_envs_total": n_total, "horizon": a.horizon,
+                   "hidden": a.hidden, "minibatch_global": tr.global_minibatch,
+                   "minibatch_rows_per_gpu": tr.mb_local, "dp_minibatch": tr.dp_minibatch,
+                   "minibatch_sampler": tr.sampler, "epochs": a.epochs,
+                   "d_capture": a.d_capture, "parallelism": f"dp{n_gpus}"},
+        "ppo_updates_per_s": a.steps / elapsed,
+        "rollout_env_steps_per_s": n_total * a.horizon / (rollout_ms * 1e-3),
+        "rollout_ms": rollout_ms, "gae_ms": gae_ms, "update_ms": update_ms,
+        "minibatch_steps_per_s": n_minibatches / (update_ms * 1e-3),
+        "episodes_finished_total": float(stats[0]),
+    }
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, tr, stats)
+    if a.full:                               # (continues training: after the dump)
+        line = full_report(a, world, rank, pg, tr, line, barrier)
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if pg is not None:
+        dist.destroy_process_group()
+
+
+DUMP_ROWS = 65536              # rollout rows a dump samples (~8 MB over the eight arrays)
+
+
+def dump_outputs(path, tr, stats):
+    """What the last timed iteration handed back, as <path>/<name>.npy
+    (float32; `stats` and `sample_index` float64): `stats`, the env statistics
+    tr.iteration() returned; `params`, the learner's flat parameter vector
+    after the iteration's update; and the iteration's rollout table (obs, act,
+    logp, rew, done, values, adv, vtarget) at DUMP_ROWS rows (t * N + env,
+    listed in `sample_index`) drawn once by a generator seeded with 0, so the
+    same arguments always sample the same rows (t >= 1: finish_iteration has
+    put the next rollout's first observation into obs[0]).  `obs` / `values`
+    are the rows' s_t / V(s_t).  Call it before anything else touches the
+    trainer."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    buf, T, N = tr.buf, tr.T, tr.N
+    lo = N if T > 1 else 0       # (obs[0] already holds the next rollout's first observation)
+    rows = np.sort(np.random.default_rng(0).integers(lo, T * N, min(T * N, DUMP_ROWS)))
+    idx = torch.from_numpy(rows).to(buf.rew.device)
+    out = {"stats": np.asarray(stats, dtype=np.float64), "sample_index": rows.astype(np.float64),
+           "params": tr.learner.P.detach().cpu().numpy()}
+    for name in ("obs", "act", "logp", "rew", "done", "values", "adv", "vtarget"):
+        t = getattr(buf, name)[:T]
+        out[name] = t.reshape(T * N, *t.shape[2:])[idx].to(torch.float32).cpu().numpy()
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+def full_report(a, world, rank, pg, tr, line, barrier):
+    """--full: everything beyond the headline, measured after the timed
+    region on the trainer the timed iterations used.  Returns rank 0's line
+    (`line` plus these measurements); None on the other ranks."""
+    import torch
+    import torch.distributed as dist
+    from satrl.trainer import VecTrainer, args_param
+    n_gpus = line["n_gpus"]
 
     # ---- roofline of the dominant kernel (satrl_ppo_rowpass, ~55% of the update).
     # Live, in the update's own conditions: eager minibatch steps (rowpass ->
@@ -862,9 +948,7 @@ def run(a, world):
                                        f"minibatch {a.minibatch}) has {steps_c3} global minibatch steps per update"}
         dp_out = {"data_parallel": dp}
 
-    rollout_ms = sum(timers["rollout_ms"]) / len(timers["rollout_ms"])
-    update_ms = sum(timers["update_ms"]) / len(timers["update_ms"])
-    gae_ms = sum(timers["gae_ms"]) / len(timers["gae_ms"])
+    rollout_ms, update_ms = line["rollout_ms"], line["update_ms"]      # of the timed iterations
     H = a.hidden
     flop_per_transition_epoch = 6 * (18 * H + H * H + 3 * H) + 6 * (18 * H + H * H + H)
     upd_flops = a.num_envs * a.horizon * a.epochs * flop_per_transition_epoch
@@ -890,24 +974,10 @@ def run(a, world):
         cpu = cpu_baseline(a.cpu_baseline_seconds, a.num_envs, a.horizon, a.hidden, a.minibatch,
                            a.epochs) if host_baseline else None
         rd_cpu_ms = rd_cpu_baseline() if host_baseline else None
-        out = {
-            "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": n_gpus, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f64+f32",
-            "data": "synthetic: reference reset state, random-init (orthogonal, seed 0) policies",
-            "config": {"workload": workload_name(a, n_gpus),
-                       "num_envs_per_gpu": a.num_envs, "num_envs_total": n_total, "horizon": a.horizon,
-                       "hidden": a.hidden, "minibatch_global": tr.global_minibatch,
-                       "minibatch_rows_per_gpu": tr.mb_local, "dp_minibatch": tr.dp_minibatch,
-                       "minibatch_sampler": tr.sampler, "epochs": a.epochs,
-                       "d_capture": a.d_capture, "parallelism": f"dp{n_gpus}"},
-            "ppo_updates_per_s": a.steps / elapsed,
-            "rollout_env_steps_per_s": n_total * a.horizon / (rollout_ms * 1e-3),
+        out = dict(line)
+        out.update({
             "rollout_sweep_num_envs": rollout_sweep,
-            "rollout_ms": rollout_ms, "gae_ms": gae_ms, "update_ms": update_ms,
             "env_kernel_env_steps_per_s": a.num_envs / (env_us * 1e-6),
-            "minibatch_steps_per_s": n_minibatches / (update_ms * 1e-3),
-            "episodes_finished_total": float(stats[0]),
             "roofline": {"kernel": (f"satrl_ppo_rowpass_dw2<{a.hidden},{a.hidden // 16}> (hand-written HIP, f32 MFMA "
                                     "16x16x4; the dW2 product fused in)" if st.fused_dw2 else
                                     f"satrl_ppo_rowpass{'_kx' if st.kx(mb_local) else ''}<{a.hidden},{a.hidden // 16}> "
@@ -988,7 +1058,7 @@ def run(a, world):
                                 "flop_per_transition_epoch": flop_per_transition_epoch},
             "roofline_policy": policy_roof,
             "cpu_baseline": cpu,
-        }
+        })
         if world == 1:
             out.update({
                 "propagators": {"rk4_j2_state_steps_per_s": a.num_envs * rk_steps / (rk4_ms * 1e-3),
@@ -1018,9 +1088,8 @@ def run(a, world):
                                      "grid_plus_fit_orbits_per_s": rd_sets / ((rd_ms + ell_ms) * 1e-3),
                                      "cpu_oracle_ms_per_curve_fitting": rd_cpu_ms[1] if rd_cpu_ms else None}})
         out.update(dp_out)
-        print(json.dumps(out), flush=True)
-    if pg is not None:
-        dist.destroy_process_group()
+        return out
+    return None
 
 
 if __name__ == "__main__":
