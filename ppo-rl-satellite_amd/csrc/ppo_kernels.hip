@@ -20,6 +20,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "philox_device.h"
@@ -594,6 +595,368 @@ __device__ __forceinline__ void store_rows(float* __restrict__ out, int ld, int 
 // measured no faster, EXPERIMENTS.md round 3).
 __device__ __forceinline__ void rp_barrier() { __syncthreads(); }
 
+// ---------------------------------------------------------------------------
+// The phases that rowpass_kernel (its forward part through mlp_forward) and
+// the column-split rowpass_cs_kernel both run, written once: the column-split
+// kernel is the RT = CT = 1, R = kRowsShort instantiation, so its values are
+// the 16-wave kernel's by construction.  The two kernels lay their shared
+// memory out differently, so every LDS array comes as a reference.
+// n0: the first hidden column of the wave's tiles.
+// ---------------------------------------------------------------------------
+// The head's scalars (mean_layer bias, log_std, fc3 bias) and its
+// per-dimension constants (var = exp(log_std)^2, log std, 1/var), off the
+// head's dependency chain: lanes 0-3 of the last wave (no row load of its
+// own at H = 256) load them as per-lane vector loads (head_load, at the top of
+// the kernel) and compute the constants into LDS during the gather
+// (head_consts; the barriers of the forward pass publish them).  Uniform
+// scalar loads of P here would make the wave's first s_waitcnt lgkmcnt -- the
+// one for the kernel arguments -- wait for them before any row load is issued.
+template <int H, int NT>
+__device__ __forceinline__ void head_load(const float* __restrict__ P, float& hls_d, float& hb3_d) {
+  const Layout L = layout(H);
+  const int hd = (int)threadIdx.x - (NT - 64);                     // head-scalar lane of the last wave
+  hls_d = 0.0f;
+  hb3_d = 0.0f;
+  if (hd >= 0 && hd < 4) {
+    hb3_d = P[hd < 3 ? L.b3a + hd : L.b3c];
+    hls_d = P[L.ls + (hd < 3 ? hd : 0)];
+  }
+}
+template <int NT>
+__device__ __forceinline__ void head_consts(float& hls_d, float& hb3_d, float (&hcs)[3][3], float (&hb3s)[4]) {
+  // (opaque to the compiler and ordered after the row loads: otherwise it
+  // hoists this arithmetic next to its loads at the top of the kernel,
+  // and the whole wave waits for them before issuing any row load)
+  asm volatile("" : "+v"(hls_d), "+v"(hb3_d)::"memory");
+  const int hd = (int)threadIdx.x - (NT - 64);
+  if (hd >= 0 && hd < 4) {
+    hb3s[hd] = hb3_d;                                               // b3a[0..2], b3c
+    if (hd < 3) {
+      const float sd = expf(hls_d), var = sd * sd;
+      hcs[0][hd] = var;
+      hcs[1][hd] = logf(sd);
+      hcs[2][hd] = 1.0f / var;
+    }
+  }
+}
+
+// rows r0 .. r0 + R of the minibatch (staged: src rows; else src[idx[row]])
+// -> S (the state) and ax (a, logp_old, adv, v_target), thread t0 of nt; the
+// head's constants on the way
+template <int R, int NT, int LDS_S>
+__device__ __forceinline__ void gather_rows(int mb, const float* __restrict__ src, const int64_t* __restrict__ idx,
+                                            int r0, int t0, int nt, float (&S)[R][LDS_S], float (&ax)[R][8],
+                                            float& hls_d, float& hb3_d, float (&hcs)[3][3], float (&hb3s)[4]) {
+  if (idx == nullptr) {
+    // contiguous (staged) rows: one 16-B load per thread covers the block's
+    // R x 32 floats, all in flight at once (a loop of dependent scalar
+    // loads took four load round trips at H = 64's 256 threads)
+    // (branch-free: rows past the minibatch load its last row, zeroed below)
+    static_assert(R * 8 <= NT, "one float4 per thread");
+    const int r = (t0 >> 3) & (R - 1), c4 = t0 & 7, row = r0 + r;
+    const bool in = t0 < R * 8;
+    float4 v = reinterpret_cast<const float4*>(src)[(int64_t)(row < mb ? row : mb - 1) * 8 + c4];
+    head_consts<NT>(hls_d, hb3_d, hcs, hb3s);
+    if (row >= mb) v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (in) {
+      const float e4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = 4 * c4 + e;                                  // s | a, logp_old, adv, v_target | pad
+        if (c < 18) S[r][c] = e4[e];
+        else if (c < 26) ax[r][c - 18] = e4[e];
+      }
+    }
+  } else {
+    for (int q = t0; q < R * 26; q += nt) {
+      const int r = q / 26, c = q % 26, row = r0 + r;
+      const float v = row < mb ? src[idx[row] * 32 + c] : 0.0f;
+      if (c < 18) S[r][c] = v; else ax[r][c - 18] = v;
+    }
+    head_consts<NT>(hls_d, hb3_d, hcs, hb3s);
+  }
+}
+
+// columns 18.. of S: the bias column of W1aug (rows of the minibatch), zero pad
+template <int NT, int R, int LDS_S>
+__device__ __forceinline__ void pad_rows(float (&S)[R][LDS_S], int nvalid) {
+  for (int q = threadIdx.x; q < R * (LDS_S - 18); q += NT) {
+    const int r = q / (LDS_S - 18), c = 18 + q % (LDS_S - 18);
+    S[r][c] = (c == 18 && r < nvalid) ? 1.0f : 0.0f;
+  }
+}
+
+// acc = tanh(acc + fc2 bias) for a wave's CT column tiles, and the tiles'
+// output-layer partials -> part[row][output][tile0 + t].  li, lg: the lane's
+// l & 15 and l >> 4, from the caller (recomputed here, the compiler no longer
+// shares the forward pass's address arithmetic: the policy kernels' register
+// counts moved).  One partial per
+// 16-column tile (DPP row sums), so the output layer sums the same H/16
+// partials in the same order whatever the wave count: the 8-wave policy
+// kernel's log-probs are the 16-wave rowpass's bit for bit
+template <int RT, int CT, int LD>
+__device__ __forceinline__ void fc2_out_partials(f4 (&acc)[RT][CT], const float (&b2v)[CT], const float (&w3)[CT][3],
+                                                 int net, int li, int lg, float (&part)[16 * RT][3][LD], int tile0) {
+  const int NQ = net == 0 ? 3 : 1;                                  // output columns of this net
+  float p[3][CT][RT][4];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float h = tanh_f32(acc[rt][t][j] + b2v[t]);           // fc2 + tanh
+        acc[rt][t][j] = h;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) p[q][t][rt][j] = fmaf(h, w3[t][q], 0.0f);
+      }
+  // the DPP row sums; NQ is uniform per workgroup (3 actor, 1 critic)
+  constexpr int NP = CT * RT * 4;                                   // partials per output column
+  float ps[3 * NP];
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ps[((q * CT + t) * RT + rt) * 4 + j] = p[q][t][rt][j];
+  if (NQ == 3) {
+    row16_sum_n<3 * NP>(ps);
+  } else {
+    float p0[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) p0[k] = ps[k];
+    row16_sum_n<NP>(p0);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) ps[k] = p0[k];
+  }
+  if (li == 0) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      if (q >= NQ) break;
+#pragma unroll
+      for (int t = 0; t < CT; ++t)
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            part[16 * rt + 4 * lg + j][q][tile0 + t] = ps[((q * CT + t) * RT + rt) * 4 + j];
+    }
+  }
+}
+
+// output-layer pre-activation of row r, column d: the NTL column-tile
+// partials in fixed order
+template <int NTL, int OSP>
+__device__ __forceinline__ float out_sum(const float (*osum)[3][OSP], int r, int d) {
+  float od = 0.0f;
+#pragma unroll
+  for (int k = 0; k < NTL; ++k) od += osum[r][d][k];
+  return od;
+}
+
+// The net's loss and its gradient for the block's R rows (threads 0 .. R-1,
+// in wave 0): dz3s[r] = d loss / d (output-layer pre-activations), and, where
+// `store`, the block's b3a / log_std / b3c partials to its tail slab tp and
+// the actor's per-row ratio to ratio_out (nullable).  STAMP: phase stamps
+// 12-14 (the probe build of rowpass_kernel).
+template <int H, int R, bool STAMP, int OSP>
+__device__ __forceinline__ void loss_head(int mb, int r0, int net, float inv_mb, float epsilon, float ent_coef,
+                                          float max_action, const float (&osum)[R][3][OSP],
+                                          const float (&hcs)[3][3], const float (&hb3s)[4], const float (&ax)[R][8],
+                                          float (&dz3s)[R][4], float* tp, float* ratio_out, bool store) {
+  const int r = threadIdx.x, row = r0 + r;
+  if (r >= R) return;
+  float dz[4] = {0.f, 0.f, 0.f, 0.f}, dls[4] = {0.f, 0.f, 0.f, 0.f};
+  if (row < mb) {
+    const float inv = inv_mb;                                     // 1.0f / (float)mb, IEEE on the host
+    if (net == 0) {                                                // actor: clipped surrogate + entropy
+      float th[3], mu[3], dv[3], var[3], logp[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        th[d] = tanh_f32(out_sum<H / 16>(osum, r, d) + hb3s[d]);
+        mu[d] = max_action * th[d];                                // 1.6 * tanh(mean_layer)
+        var[d] = hcs[0][d];
+        dv[d] = ax[r][d] - mu[d];
+        // (the forward expression of gaussian_act, bit for bit: logp_old)
+        logp[d] = (-(dv[d] * dv[d]) / (2.0f * var[d]) - hcs[1][d]) - kLogSqrt2Pi;
+      }
+      if constexpr (STAMP) PHASE_PROBE(12);
+      const float lsum = (logp[0] + logp[1]) + logp[2];
+      const float lold = (ax[r][3] + ax[r][4]) + ax[r][5];
+      const float ratio = expf(lsum - lold);
+      if (ratio_out != nullptr && store) ratio_out[row] = ratio;   // (satrl_ppo_rowpass_ratio)
+      const float adv = ax[r][6];
+      const float s1 = ratio * adv;
+      const float cr = fminf(fmaxf(ratio, 1.0f - epsilon), 1.0f + epsilon);
+      const float s2 = cr * adv;
+      const float g1 = s1 < s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);   // torch.min tie split
+      const float g2 = s2 < s1 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
+      const float inside = (ratio >= 1.0f - epsilon && ratio <= 1.0f + epsilon) ? 1.0f : 0.0f;
+      const float dmin = -inv;
+      const float dratio = dmin * g1 * adv + dmin * g2 * adv * inside;
+      const float dlsum = dratio * ratio;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const float dvv = dv[d] * hcs[2][d];                       // (x - mu) / var
+        const float dmu = dlsum * dvv;
+        dz[d] = (dmu * max_action) * (1.0f - th[d] * th[d]);
+        dls[d] = dlsum * (dv[d] * dvv - 1.0f) - ent_coef * inv;
+      }
+    } else {                                                       // critic: MSE
+      const float vc = out_sum<H / 16>(osum, r, 0) + hb3s[3];
+      dz[3] = 2.0f * inv * (vc - ax[r][7]);                        // d mse / d v
+    }
+  }
+  if constexpr (STAMP) PHASE_PROBE(13);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) dz3s[r][q] = dz[q];
+  // the block's b3a / log_std / b3c partials: sums over its R rows, reduced
+  // across these R lanes of wave 0 in a fixed order: DPP sums of each
+  // 16-lane row, then row 0 + row 1 (readlane), no LDS round trips
+  static_assert(R == 16 || R == 32, "row sums cover one or two DPP rows");
+  float red[7] = {dz[0], dz[1], dz[2], dls[0], dls[1], dls[2], dz[3]};
+  row16_sum_n<7>(red);
+  if (R == 32) {
+#pragma unroll
+    for (int q = 0; q < 7; ++q)
+      red[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(red[q]), 0)) +
+               __int_as_float(__builtin_amdgcn_readlane(__float_as_int(red[q]), 16));
+  }
+  if constexpr (STAMP) PHASE_PROBE(14);
+  if (r == 0 && store) {
+    if (net == 0) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        tp[5 * H + q] = red[q];          // b3a
+        tp[5 * H + 4 + q] = red[3 + q];  // log_std
+      }
+      tp[5 * H + 3] = 0.0f;
+      tp[5 * H + 7] = 0.0f;
+    } else {
+      tp[6 * H + 8] = red[6];            // b3c
+      tp[6 * H + 9] = 0.0f; tp[6 * H + 10] = 0.0f; tp[6 * H + 11] = 0.0f;
+    }
+  }
+}
+
+// The tail of phase C for a wave's CT column tiles at n0: dZ2 = (dz3s W3)
+// (1 - tanh(fc2)^2) -> d2v, its LDS image (f32 rows dzs, or at the split-bf16
+// width the planes dzp -- row stride LDP, plane stride PS -- with the split
+// words kept in d2w), and the block's db2 /
+// dW3 partials -> the tail slab tp.  Unswitched on the (workgroup-uniform)
+// net: no per-element branches, and the critic skips the actor's three
+// output columns.  (Moving the db2 / dW3 partial sums into phase D's MFMA gaps
+// measured slower: D +2.6 k cycles for 0.5 k saved here, EXPERIMENTS.md
+// round 4.)
+template <int H, int RT, int CT, int LDP, int PS, bool ACT>
+__device__ __forceinline__ void tail_net(const f4 (&acc)[RT][CT], const float (&w3)[CT][3],
+                                         const float (&dz3s)[16 * RT][4], float* dzs, unsigned short* dzp,
+                                         float (&d2v)[RT][CT][4], unsigned (&d2w)[RT][CT][6], float* tp,
+                                         int net, int n0) {
+  const int l = threadIdx.x & 63, li = l & 15, lg = l >> 4;
+  constexpr bool BF3 = kBf3<H>;
+  constexpr int LDA = H + 4;                                       // row stride of dzs
+  constexpr int NC = ACT ? 3 : 1;
+#pragma unroll
+  for (int t = 0; t < CT; ++t) {
+    const int n = n0 + 16 * t + li;
+    float cb2 = 0.f, cw[NC];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) cw[q] = 0.f;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = 16 * rt + 4 * lg + j;
+        const float h = acc[rt][t][j];
+        float dh;
+        if constexpr (ACT) dh = (dz3s[r][0] * w3[t][0] + dz3s[r][1] * w3[t][1]) + dz3s[r][2] * w3[t][2];
+        else dh = dz3s[r][3] * w3[t][0];
+        const float d2 = dh * (1.0f - h * h);                     // tanh backward
+        if constexpr (!BF3) dzs[r * LDA + n] = d2;
+        d2v[rt][t][j] = d2;
+        cb2 += d2;
+        if constexpr (ACT) {
+          cw[0] = fmaf(dz3s[r][0], h, cw[0]); cw[1] = fmaf(dz3s[r][1], h, cw[1]); cw[2] = fmaf(dz3s[r][2], h, cw[2]);
+        } else {
+          cw[0] = fmaf(dz3s[r][3], h, cw[0]);
+        }
+      }
+      // (split-bf16) dZ2's LDS planes (phase D's A operand), split once as
+      // pairs; the words stay in d2w for the k-packed dZ2 store
+      if constexpr (BF3) put3_col4<PS, LDP>(dzp, (16 * rt + 4 * lg) * LDP + n, d2v[rt][t], d2w[rt][t]);
+    }
+    cb2 = xor32_sum(xor16_sum(cb2));
+#pragma unroll
+    for (int q = 0; q < NC; ++q) cw[q] = xor32_sum(xor16_sum(cw[q]));
+    if (lg == 0) {
+      tp[net * H + n] = cb2;                                     // db2
+      if constexpr (ACT) {                                       // dW3a
+        tp[2 * H + n] = cw[0]; tp[3 * H + n] = cw[1]; tp[4 * H + n] = cw[2];
+      } else {
+        tp[5 * H + 8 + n] = cw[0];                               // dW3c
+      }
+    }
+  }
+}
+template <int H, int RT, int CT, int LDP, int PS>
+__device__ __forceinline__ void tail(const f4 (&acc)[RT][CT], const float (&w3)[CT][3],
+                                     const float (&dz3s)[16 * RT][4], float* dzs, unsigned short* dzp,
+                                     float (&d2v)[RT][CT][4], unsigned (&d2w)[RT][CT][6], float* tp,
+                                     int net, int n0) {
+  if (net == 0) tail_net<H, RT, CT, LDP, PS, true>(acc, w3, dz3s, dzs, dzp, d2v, d2w, tp, net, n0);
+  else tail_net<H, RT, CT, LDP, PS, false>(acc, w3, dz3s, dzs, dzp, d2v, d2w, tp, net, n0);
+}
+
+// Phase E for a wave's CT column tiles at n0: dZ1 = dH1 (1 - H1^2) in place,
+// then [dW1 | db1][n][k'] = sum_r dZ1[r][n] S[r][k'] -> pw.
+// acc[rt][t][j] = dZ1[row 16rt+4lg+j][n0+16t+li] is the A operand A[n][r] of
+// the product (k = row, kk = j); B[r][k'] = S[16rt+4lg+kk][16hb + li] from LDS.
+template <int RT, int CT, int LDS_S>
+__device__ __forceinline__ void phase_e(f4 (&acc)[RT][CT], const float (&h1)[RT][CT][4],
+                                        const float (&S)[16 * RT][LDS_S], float* pw, int n0) {
+  const int l = threadIdx.x & 63, li = l & 15, lg = l >> 4;
+#pragma unroll
+  for (int t = 0; t < CT; ++t) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[rt][t][j] = acc[rt][t][j] * (1.0f - h1[rt][t][j] * h1[rt][t][j]);
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb) {
+      f4 d = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) d = mfma4(acc[rt][t][kk], S[16 * rt + 4 * lg + kk][16 * hb + li], d);
+      // d[j] = dW1aug[n = n0 + 16t + 4lg + j][k' = 16hb + li]
+      const int kp = 16 * hb + li;
+      if (kp < 20) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pw[(int64_t)(n0 + 16 * t + 4 * lg + j) * 20 + kp] = d[j];
+      }
+    }
+  }
+}
+
+// (k-packed) a wave's tiles of the block's H1 planes, from the split words
+// h1w, and the zero rows of the padded 32-row chunk past a 16-row kernel's
+// last block, in H1 and dZ2 (rows past the minibatch: zero inputs, so
+// tanh(fc1) = 0 and dZ2 = 0 there).  The 16-row kernels write through (st_kx).
+template <int H, int R, int CT>
+__device__ __forceinline__ void h1_kx(unsigned short* __restrict__ H1x, unsigned short* __restrict__ dZ2x, int net,
+                                      int mb, int r0, int n0, const unsigned (&h1w)[R / 16][CT][6]) {
+  const int64_t PLX = kx_rows(mb) * H;                             // plane elements per net
+  store_kx_w<H, R, CT, R == kRowsShort>(H1x + net * 3 * PLX, PLX, r0, n0, h1w);
+  if (R < 32 && r0 + R < kx_rows(mb) && r0 + R >= mb) {            // (uniform) the padded chunk's rows past this block
+    const float z[R / 16][CT][4] = {};
+    store_kx<H, R, CT>(H1x + net * 3 * PLX, PLX, r0 + R, n0, z);
+    store_kx<H, R, CT>(dZ2x + net * 3 * PLX, PLX, r0 + R, n0, z);
+  }
+}
+
 // Shared-memory block and forward pass (phases A, B and the output-layer dot
 // products of C) common to rowpass_kernel and policy_kernel, so the rollout's
 // policy/value forward and the update's forward are the same instructions in
@@ -671,10 +1034,7 @@ __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* 
     }
   }
   gather(tid, NT);
-  for (int q = tid; q < R * (LDS_S - 18); q += NT) {
-    const int r = q / (LDS_S - 18), c = 18 + q % (LDS_S - 18);
-    sm.S[r][c] = (c == 18 && r < nvalid) ? 1.0f : 0.0f;           // bias column of W1aug, zero pad
-  }
+  pad_rows<NT>(sm.S, nvalid);
   PHASE_PROBE(8);
   rp_barrier();
   PHASE_PROBE(9);
@@ -732,68 +1092,9 @@ __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* 
   PHASE_PROBE(2);
 
   // ---- C (forward part): fc2 tanh, output-layer dot products -----------------
-  const int NQ = net == 0 ? 3 : 1;                                  // output columns of this net
-  // one partial per 16-column tile (DPP row sums), so the output layer sums
-  // the same H/16 partials in the same order whatever the wave count: the
-  // 8-wave policy kernel's log-probs are the 16-wave rowpass's bit for bit
-  float p[3][CT][RT][4];
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-    for (int t = 0; t < CT; ++t)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float h = tanh_f32(acc[rt][t][j] + b2v[t]);           // fc2 + tanh
-        acc[rt][t][j] = h;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) p[q][t][rt][j] = fmaf(h, w3[t][q], 0.0f);
-      }
-  // the DPP row sums; NQ is uniform per workgroup (3 actor, 1 critic)
-  constexpr int NP = CT * RT * 4;                                   // partials per output column
-  float ps[3 * NP];
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
-#pragma unroll
-    for (int t = 0; t < CT; ++t)
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ps[((q * CT + t) * RT + rt) * 4 + j] = p[q][t][rt][j];
-  if (NQ == 3) {
-    row16_sum_n<3 * NP>(ps);
-  } else {
-    float p0[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) p0[k] = ps[k];
-    row16_sum_n<NP>(p0);
-#pragma unroll
-    for (int k = 0; k < NP; ++k) ps[k] = p0[k];
-  }
-  if (li == 0) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      if (q >= NQ) break;
-#pragma unroll
-      for (int t = 0; t < CT; ++t)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            sm.osum[16 * rt + 4 * lg + j][q][w * CT + t] = ps[((q * CT + t) * RT + rt) * 4 + j];
-    }
-  }
+  fc2_out_partials(acc, b2v, w3, net, li, lg, sm.osum, w * CT);
   rp_barrier();
   PHASE_PROBE(3);
-}
-
-// output-layer pre-activation of row r, column d: the NTL column-tile
-// partials in fixed order
-template <int NTL, int OSP>
-__device__ __forceinline__ float out_sum(const float (*osum)[3][OSP], int r, int d) {
-  float od = 0.0f;
-#pragma unroll
-  for (int k = 0; k < NTL; ++k) od += osum[r][d][k];
-  return od;
 }
 
 template <int H, int NW, int R = kRows, bool FDW2 = false, bool KX = false, bool SPAN = false>
@@ -848,71 +1149,17 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   }
 #endif
   PHASE_PROBE(0);
-  // The head's scalars (mean_layer bias, log_std, fc3 bias) and its
-  // per-dimension constants (var = exp(log_std)^2, log std, 1/var), off the
-  // head's dependency chain: lanes 0-3 of the last wave (no row load of its
-  // own at H = 256) load them as per-lane vector loads and compute the
-  // constants into LDS during the gather (the barriers of the forward pass
-  // publish them).  Uniform scalar loads of P here would make the wave's
-  // first s_waitcnt lgkmcnt -- the one for the kernel arguments -- wait for
-  // them before any row load is issued.
-  __shared__ float hcs[3][3];
-  __shared__ float hb3s[4];                                        // b3a[0..2], b3c
-  const int hd = tid - (NT - 64);                                  // head-scalar lane of the last wave
-  float hls_d = 0.0f, hb3_d = 0.0f;
-  if (hd >= 0 && hd < 4) {
-    hb3_d = P[hd < 3 ? L.b3a + hd : L.b3c];
-    hls_d = P[L.ls + (hd < 3 ? hd : 0)];
-  }
+  __shared__ float hcs[3][3];                                      // the head's constants (head_load)
+  __shared__ float hb3s[4];
+  float hls_d, hb3_d;
+  head_load<H, NT>(P, hls_d, hb3_d);
 
   f4 acc[RT][CT];
   float h1[RT][CT][4];
   float w3[CT][3];
   unsigned h1w[RT][CT][6];                                         // (split-bf16) the split H1 words
   auto gather = [&](int t0, int nt) {
-    auto head_consts = [&] {
-      // (opaque to the compiler and ordered after the row loads: otherwise it
-      // hoists this arithmetic next to its loads at the top of the kernel,
-      // and the whole wave waits for them before issuing any row load)
-      asm volatile("" : "+v"(hls_d), "+v"(hb3_d)::"memory");
-      if (hd >= 0 && hd < 4) {
-        hb3s[hd] = hb3_d;
-        if (hd < 3) {
-          const float sd = expf(hls_d), var = sd * sd;
-          hcs[0][hd] = var;
-          hcs[1][hd] = logf(sd);
-          hcs[2][hd] = 1.0f / var;
-        }
-      }
-    };
-    if (idx == nullptr) {
-      // contiguous (staged) rows: one 16-B load per thread covers the block's
-      // R x 32 floats, all in flight at once (a loop of dependent scalar
-      // loads took four load round trips at H = 64's 256 threads)
-      // (branch-free: rows past the minibatch load its last row, zeroed below)
-      static_assert(R * 8 <= NT, "one float4 per thread");
-      const int r = (t0 >> 3) & (R - 1), c4 = t0 & 7, row = r0 + r;
-      const bool in = t0 < R * 8;
-      float4 v = reinterpret_cast<const float4*>(src)[(int64_t)(row < mb ? row : mb - 1) * 8 + c4];
-      head_consts();
-      if (row >= mb) v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (in) {
-        const float e4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = 4 * c4 + e;                                  // s | a, logp_old, adv, v_target | pad
-          if (c < 18) S[r][c] = e4[e];
-          else if (c < 26) ax[r][c - 18] = e4[e];
-        }
-      }
-    } else {
-      for (int q = t0; q < R * 26; q += nt) {
-        const int r = q / 26, c = q % 26, row = r0 + r;
-        const float v = row < mb ? src[idx[row] * 32 + c] : 0.0f;
-        if (c < 18) S[r][c] = v; else ax[r][c - 18] = v;
-      }
-      head_consts();
-    }
+    gather_rows<R, NT>(mb, src, idx, r0, t0, nt, S, ax, hls_d, hb3_d, hcs, hb3s);
   };
   // the fc2 operand image: the f32 W2^T
   const float* W2T = static_cast<const float*>(W2X);
@@ -925,19 +1172,12 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   mlp_forward<H, NW, R, true, FDW2>(sm, P, net, mb - r0, gather,
                                    FDW2 || KX || BF3 ? nullptr : H1g + ((int64_t)net * mb + r0) * H, acc, h1, w3,
                                    h1w);
-  // (rows past the minibatch: zero inputs, so tanh(fc1) = 0 and dZ2 = 0 there)
   // (KX) the H1 planes: wave 0, which runs the loss head next, stores its
   // share after the head's barrier, off the head's path; the other waves now
-  auto h1_kx = [&] {
-    store_kx_w<H, R, CT, R == kRowsShort>(reinterpret_cast<unsigned short*>(H1g) + net * 3 * PLX, PLX, r0, n0, h1w);
-    if (R < 32 && r0 + R < kx_rows(mb) && r0 + R >= mb) {            // (uniform) the padded chunk's rows past this block
-      const float z[R / 16][CT][4] = {};
-      store_kx<H, R, CT>(reinterpret_cast<unsigned short*>(H1g) + net * 3 * PLX, PLX, r0 + R, n0, z);
-      store_kx<H, R, CT>(reinterpret_cast<unsigned short*>(dZ2g) + net * 3 * PLX, PLX, r0 + R, n0, z);
-    }
-  };
+  unsigned short* const H1x = reinterpret_cast<unsigned short*>(H1g);
+  unsigned short* const dZ2x = reinterpret_cast<unsigned short*>(dZ2g);
   if constexpr (KX) {
-    if (w != 0) h1_kx();
+    if (w != 0) h1_kx<H, R, CT>(H1x, dZ2x, net, mb, r0, n0, h1w);
   }
   else if constexpr (BF3 && !FDW2) store_rows<R, CT>(H1g + ((int64_t)net * mb + r0) * H, H, n0, mb - r0, h1);
   // phase D's first W2T chunks go out now, under the loss head and the tail
@@ -945,81 +1185,9 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   mfma_rows_pre<H, CT>(W2T + (int64_t)net * H * H, n0, preD);
 
   // ---- C: the net's loss and its gradient, dZ2 ---------------------------------
-  if (tid < R) {
-    const int r = tid, row = r0 + r;
-    float dz[4] = {0.f, 0.f, 0.f, 0.f}, dls[4] = {0.f, 0.f, 0.f, 0.f};
-    if (row < mb) {
-      const float inv = inv_mb;                                   // 1.0f / (float)mb, IEEE on the host
-      if (net == 0) {                                              // actor: clipped surrogate + entropy
-        float th[3], mu[3], dv[3], var[3], logp[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          th[d] = tanh_f32(out_sum<H / 16>(sm.osum, r, d) + hb3s[d]);
-          mu[d] = max_action * th[d];                              // 1.6 * tanh(mean_layer)
-          var[d] = hcs[0][d];
-          dv[d] = ax[r][d] - mu[d];
-          // (the forward expression of gaussian_act, bit for bit: logp_old)
-          logp[d] = (-(dv[d] * dv[d]) / (2.0f * var[d]) - hcs[1][d]) - kLogSqrt2Pi;
-        }
-        PHASE_PROBE(12);
-        const float lsum = (logp[0] + logp[1]) + logp[2];
-        const float lold = (ax[r][3] + ax[r][4]) + ax[r][5];
-        const float ratio = expf(lsum - lold);
-        if (ratio_out != nullptr) ratio_out[row] = ratio;          // (satrl_ppo_rowpass_ratio)
-        const float adv = ax[r][6];
-        const float s1 = ratio * adv;
-        const float cr = fminf(fmaxf(ratio, 1.0f - epsilon), 1.0f + epsilon);
-        const float s2 = cr * adv;
-        const float g1 = s1 < s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);   // torch.min tie split
-        const float g2 = s2 < s1 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-        const float inside = (ratio >= 1.0f - epsilon && ratio <= 1.0f + epsilon) ? 1.0f : 0.0f;
-        const float dmin = -inv;
-        const float dratio = dmin * g1 * adv + dmin * g2 * adv * inside;
-        const float dlsum = dratio * ratio;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          const float dvv = dv[d] * hcs[2][d];                     // (x - mu) / var
-          const float dmu = dlsum * dvv;
-          dz[d] = (dmu * max_action) * (1.0f - th[d] * th[d]);
-          dls[d] = dlsum * (dv[d] * dvv - 1.0f) - ent_coef * inv;
-        }
-      } else {                                                     // critic: MSE
-        const float vc = out_sum<H / 16>(sm.osum, r, 0) + hb3s[3];
-        dz[3] = 2.0f * inv * (vc - ax[r][7]);                      // d mse / d v
-      }
-    }
-    PHASE_PROBE(13);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dz3s[r][q] = dz[q];
-    // the block's b3a / log_std / b3c partials: sums over its R rows, reduced
-    // across these R lanes of wave 0 in a fixed order: DPP sums of each
-    // 16-lane row, then row 0 + row 1 (readlane), no LDS round trips
-    static_assert(R == 16 || R == 32, "row sums cover one or two DPP rows");
-    float* tp = ptail + (int64_t)rb * L.tail;
-    float red[7] = {dz[0], dz[1], dz[2], dls[0], dls[1], dls[2], dz[3]};
-    row16_sum_n<7>(red);
-    if (R == 32) {
-#pragma unroll
-      for (int q = 0; q < 7; ++q)
-        red[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(red[q]), 0)) +
-                 __int_as_float(__builtin_amdgcn_readlane(__float_as_int(red[q]), 16));
-    }
-    PHASE_PROBE(14);
-    if (r == 0) {
-      if (net == 0) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          tp[5 * H + q] = red[q];          // b3a
-          tp[5 * H + 4 + q] = red[3 + q];  // log_std
-        }
-        tp[5 * H + 3] = 0.0f;
-        tp[5 * H + 7] = 0.0f;
-      } else {
-        tp[6 * H + 8] = red[6];            // b3c
-        tp[6 * H + 9] = 0.0f; tp[6 * H + 10] = 0.0f; tp[6 * H + 11] = 0.0f;
-      }
-    }
-  }
+  float* tp = ptail + (int64_t)rb * L.tail;                         // tail-relative slab of this row block
+  loss_head<H, R, true>(mb, r0, net, inv_mb, epsilon, ent_coef, max_action, sm.osum, hcs, hb3s, ax, dz3s, tp,
+                        ratio_out, true);
   rp_barrier();
   PHASE_PROBE(4);
   // (wave 0's share of the H1 planes after the head's barrier: before it, the
@@ -1027,64 +1195,13 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   // 15 waves idle -- in-graph step 47.73-47.88 against 47.99-48.51 us over
   // four alternations, bitwise the same; EXPERIMENTS.md round 6)
   if constexpr (KX) {
-    if (w == 0) h1_kx();
+    if (w == 0) h1_kx<H, R, CT>(H1x, dZ2x, net, mb, r0, n0, h1w);
   }
-  float* tp = ptail + (int64_t)rb * L.tail;                         // tail-relative slab of this row block
   float d2v[RT][CT][4];
   unsigned d2w[RT][CT][6];                                         // (split-bf16) the split dZ2 words
-  // unswitched on the (workgroup-uniform) net: no per-element branches, and
-  // the critic skips the actor's three output columns.  (Moving the db2 /
-  // dW3 partial sums into phase D's MFMA gaps measured slower: D +2.6 k
-  // cycles for 0.5 k saved here, EXPERIMENTS.md round 4.)
-  auto tail = [&](auto actor) {
-    constexpr bool ACT = decltype(actor)::value;
-    constexpr int NC = ACT ? 3 : 1;
-#pragma unroll
-    for (int t = 0; t < CT; ++t) {
-      const int n = n0 + 16 * t + li;
-      float cb2 = 0.f, cw[NC];
-#pragma unroll
-      for (int q = 0; q < NC; ++q) cw[q] = 0.f;
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int r = 16 * rt + 4 * lg + j;
-          const float h = acc[rt][t][j];
-          float dh;
-          if constexpr (ACT) dh = (dz3s[r][0] * w3[t][0] + dz3s[r][1] * w3[t][1]) + dz3s[r][2] * w3[t][2];
-          else dh = dz3s[r][3] * w3[t][0];
-          const float d2 = dh * (1.0f - h * h);                     // tanh backward
-          if constexpr (!BF3) dzs[r][n] = d2;
-          d2v[rt][t][j] = d2;
-          cb2 += d2;
-          if constexpr (ACT) {
-            cw[0] = fmaf(dz3s[r][0], h, cw[0]); cw[1] = fmaf(dz3s[r][1], h, cw[1]); cw[2] = fmaf(dz3s[r][2], h, cw[2]);
-          } else {
-            cw[0] = fmaf(dz3s[r][3], h, cw[0]);
-          }
-        }
-        // (split-bf16) dZ2's LDS planes (phase D's A operand), split once as
-        // pairs; the words stay in d2w for the k-packed dZ2 store
-        if constexpr (BF3) put3_col4<PS, LDP>(dzp, (16 * rt + 4 * lg) * LDP + n, d2v[rt][t], d2w[rt][t]);
-      }
-      cb2 = xor32_sum(xor16_sum(cb2));
-#pragma unroll
-      for (int q = 0; q < NC; ++q) cw[q] = xor32_sum(xor16_sum(cw[q]));
-      if (lg == 0) {
-        tp[net * H + n] = cb2;                                     // db2
-        if constexpr (ACT) {                                       // dW3a
-          tp[2 * H + n] = cw[0]; tp[3 * H + n] = cw[1]; tp[4 * H + n] = cw[2];
-        } else {
-          tp[5 * H + 8 + n] = cw[0];                               // dW3c
-        }
-      }
-    }
-  };
-  if (net == 0) tail(std::true_type{});
-  else tail(std::false_type{});
+  tail<H, RT, CT, LDP, PS>(acc, w3, dz3s, &dzs[0][0], dzp, d2v, d2w, tp, net, n0);
   if constexpr (KX)
-    store_kx_w<H, R, CT, R == kRowsShort>(reinterpret_cast<unsigned short*>(dZ2g) + net * 3 * PLX, PLX, r0, n0, d2w);
+    store_kx_w<H, R, CT, R == kRowsShort>(dZ2x + net * 3 * PLX, PLX, r0, n0, d2w);
   else if constexpr (!FDW2) store_rows<R, CT>(dZ2g + ((int64_t)net * mb + r0) * H, H, n0, mb - r0, d2v);
   rp_barrier();
   PHASE_PROBE(5);
@@ -1101,30 +1218,7 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   PHASE_PROBE(6);
 
   // ---- E: dZ1 = dH1 (1 - H1^2); [dW1 | db1][n][k'] = sum_r dZ1[r][n] S[r][k'] ----
-  // acc[rt][t][j] = dZ1[row 16rt+4lg+j][n0+16t+li] is the A operand A[n][r] of
-  // the product (k = row, kk = j); B[r][k'] = S[16rt+4lg+kk][16hb + li] from LDS.
-  float* pw = pw1 + (int64_t)rb * 2 * H * 20 + (int64_t)net * H * 20;
-#pragma unroll
-  for (int t = 0; t < CT; ++t) {
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[rt][t][j] = acc[rt][t][j] * (1.0f - h1[rt][t][j] * h1[rt][t][j]);
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-      f4 d = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) d = mfma4(acc[rt][t][kk], S[16 * rt + 4 * lg + kk][16 * hb + li], d);
-      // d[j] = dW1aug[n = n0 + 16t + 4lg + j][k' = 16hb + li]
-      const int kp = 16 * hb + li;
-      if (kp < 20) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pw[(int64_t)(n0 + 16 * t + 4 * lg + j) * 20 + kp] = d[j];
-      }
-    }
-  }
+  phase_e(acc, h1, S, pw1 + (int64_t)rb * 2 * H * 20 + (int64_t)net * H * 20, n0);
   PHASE_PROBE(7);
 
   // ---- F (FDW2, H <= 128): this block's dW2 partial = dZ2^T H1 over its rows ---
@@ -1169,11 +1263,15 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
 // the tile 4j + w (columns 64j + 16w ..).  At configs[3]'s 512 rows per rank
 // rowpass_kernel<256, 16, 16> puts 64 workgroups of 16 waves on 256 CUs, four
 // waves per SIMD issuing phases B and D one after another; here 256
-// workgroups of 4 waves, one wave per SIMD.  Every value is computed by the
-// instructions of rowpass_kernel<256, 16, kRowsShort, false, true> in the same
-// order -- fc1 of all 16 tiles in every quarter (phase B's A operand is all of
-// H1), then the same per-tile fc2, output-layer, loss-head, tail, dH1 and dW1
-// sequences -- so every output is bitwise that kernel's.
+// workgroups of 4 waves, one wave per SIMD.  Every output is bitwise
+// rowpass_kernel<256, 16, kRowsShort, false, true>'s: the head scalars, row
+// gather, S padding, fc2 tanh and output-layer partials, loss head, tail,
+// phase E and the H1 plane stores are that kernel's own functions (head_load
+// .. h1_kx above) at RT = CT = 1, and phases B and D its mfma_rows3.  Written
+// out here, because its shape differs: the fc1 prologue -- every quarter
+// computes fc1 of all 16 tiles, four per wave (phase B's A operand is all of
+// H1), in mlp_forward's per-tile sequence -- and with it the loads of the
+// wave's fc2 bias and output-layer weights.
 // Two hand-offs inside the launch between the kCsSplit workgroups of a group,
 // in the form of row 3 of MI355X_MICROARCH.md's sc1 hand-off table: __device__
 // arrays; payload stores sc1 (8 B, every 128-B line by 16 lanes of one store
@@ -1241,7 +1339,7 @@ __global__ void __launch_bounds__(kCsWaves * 64) rowpass_cs_kernel(
     int mb, const float* __restrict__ src, const int64_t* __restrict__ idx, const float* __restrict__ P,
     const float* __restrict__ W2T, float epsilon, float ent_coef, float max_action,
     unsigned short* __restrict__ H1x, unsigned short* __restrict__ dZ2x, float* __restrict__ ptail,
-    float* __restrict__ pw1, float* __restrict__ ratio_out, float inv_mb, unsigned long long* __restrict__ span) {
+    float* __restrict__ pw1, float inv_mb, unsigned long long* __restrict__ span) {
   const unsigned long long span_t0 = SPAN ? satrl_span::now() : 0ull;
   constexpr int H = 256, R = kRowsShort, NT = kCsWaves * 64, LDS_S = 36;
   constexpr int LDP = MlpSmem<H, 16, R>::LDP, PS = MlpSmem<H, 16, R>::PS, OSP = MlpSmem<H, 16, R>::OSP;
@@ -1274,17 +1372,12 @@ __global__ void __launch_bounds__(kCsWaves * 64) rowpass_cs_kernel(
   unsigned* ctr = &g_cs_ctr[grp][0];
   PHASE_PROBE(0);
 
-  // head scalars: lanes 0-3 of the last wave (no row load of its own)
-  const int hd = tid - (NT - 64);
-  float hls_d = 0.0f, hb3_d = 0.0f;
-  if (hd >= 0 && hd < 4) {
-    hb3_d = P[hd < 3 ? L.b3a + hd : L.b3c];
-    hls_d = P[L.ls + (hd < 3 ? hd : 0)];
-  }
+  float hls_d, hb3_d;
+  head_load<H, NT>(P, hls_d, hb3_d);
   // fc1 weights of the wave's four fc1 tiles w, w + 4, w + 8, w + 12 (tile 4j + w
   // among them, t = j), this tile's fc2 bias and output-layer weights
   float4 w1raw[4][2];
-  float b2v, w3raw[3];
+  float b2v[1], w3raw[3];
   {
     const float* W1 = P + L.W1 + (int64_t)net * H * 20;
     const int o0 = lg < 2 ? 8 * lg : 16, o1 = lg < 2 ? 8 * lg + 4 : 16;
@@ -1295,60 +1388,20 @@ __global__ void __launch_bounds__(kCsWaves * 64) rowpass_cs_kernel(
       w1raw[t][1] = *reinterpret_cast<const float4*>(bp + o1);
     }
     const int n = n0 + li;
-    b2v = P[L.b2 + net * H + n];
+    b2v[0] = P[L.b2 + net * H + n];
     w3raw[0] = P[(net == 0 ? L.W3a : L.W3c) + n];
     w3raw[1] = P[L.W3a + H + n];
     w3raw[2] = P[L.W3a + 2 * H + n];
   }
-  // ---- A: gather (rowpass_kernel's), fc1 of all 16 tiles ---------------------
-  {
-    auto head_consts = [&] {
-      asm volatile("" : "+v"(hls_d), "+v"(hb3_d)::"memory");
-      if (hd >= 0 && hd < 4) {
-        sm.hb3s[hd] = hb3_d;
-        if (hd < 3) {
-          const float sd = expf(hls_d), var = sd * sd;
-          sm.hcs[0][hd] = var;
-          sm.hcs[1][hd] = logf(sd);
-          sm.hcs[2][hd] = 1.0f / var;
-        }
-      }
-    };
-    if (idx == nullptr) {
-      static_assert(R * 8 <= NT, "one float4 per thread");
-      const int r = (tid >> 3) & (R - 1), c4 = tid & 7, row = r0 + r;
-      const bool in = tid < R * 8;
-      float4 v = reinterpret_cast<const float4*>(src)[(int64_t)(row < mb ? row : mb - 1) * 8 + c4];
-      head_consts();
-      if (row >= mb) v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (in) {
-        const float e4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = 4 * c4 + e;
-          if (c < 18) sm.S[r][c] = e4[e];
-          else if (c < 26) sm.ax[r][c - 18] = e4[e];
-        }
-      }
-    } else {
-      for (int q = tid; q < R * 26; q += NT) {
-        const int r = q / 26, c = q % 26, row = r0 + r;
-        const float v = row < mb ? src[idx[row] * 32 + c] : 0.0f;
-        if (c < 18) sm.S[r][c] = v; else sm.ax[r][c - 18] = v;
-      }
-      head_consts();
-    }
-  }
-  for (int q = tid; q < R * (LDS_S - 18); q += NT) {
-    const int r = q / (LDS_S - 18), c = 18 + q % (LDS_S - 18);
-    sm.S[r][c] = (c == 18 && r < mb - r0) ? 1.0f : 0.0f;
-  }
+  // ---- A: gather, fc1 of all 16 tiles ----------------------------------------
+  gather_rows<R, NT>(mb, src, idx, r0, tid, NT, sm.S, sm.ax, hls_d, hb3_d, sm.hcs, sm.hb3s);
+  pad_rows<NT>(sm.S, mb - r0);
   PHASE_PROBE(8);
   rp_barrier();
   PHASE_PROBE(9);
   WPre<1> preB;
   mfma_rows_pre<H, 1>(P + L.W2 + (int64_t)net * H * H, n0, preB);
-  float w3[3];
+  float w3[1][3];
   float4 bw1[4][2];
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -1356,9 +1409,9 @@ __global__ void __launch_bounds__(kCsWaves * 64) rowpass_cs_kernel(
     bw1[t][0] = lg < 3 ? w1raw[t][0] : z4;
     bw1[t][1] = lg < 2 ? w1raw[t][1] : z4;
   }
-  w3[0] = w3raw[0];
-  w3[1] = net == 0 ? w3raw[1] : 0.0f;
-  w3[2] = net == 0 ? w3raw[2] : 0.0f;
+  w3[0][0] = w3raw[0];
+  w3[0][1] = net == 0 ? w3raw[1] : 0.0f;
+  w3[0][2] = net == 0 ? w3raw[2] : 0.0f;
   f4 a1[1][4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) a1[0][t] = f4{0.f, 0.f, 0.f, 0.f};
@@ -1389,47 +1442,11 @@ __global__ void __launch_bounds__(kCsWaves * 64) rowpass_cs_kernel(
   mfma_rows3<H, LDP, PS, H, 1, 1, true>(sm.h1p, P + L.W2 + (int64_t)net * H * H, n0, acc, &preB);
   PHASE_PROBE(2);
   // the H1 k-packed planes of this tile (and the padded chunk's zero rows)
-  auto h1_kx = [&] {
-    store_kx_w<H, R, 1, true>(H1x + net * 3 * PLX, PLX, r0, n0, h1w);
-    if (r0 + R < kx_rows(mb) && r0 + R >= mb) {
-      const float z[1][1][4] = {};
-      store_kx<H, R, 1>(H1x + net * 3 * PLX, PLX, r0 + R, n0, z);
-      store_kx<H, R, 1>(dZ2x + net * 3 * PLX, PLX, r0 + R, n0, z);
-    }
-  };
-  h1_kx();
+  h1_kx<H, R, 1>(H1x, dZ2x, net, mb, r0, n0, h1w);
   WPre<1> preD;
   mfma_rows_pre<H, 1>(W2T + (int64_t)net * H * H, n0, preD);
   // ---- C (forward): tanh(fc2), this tile's output-layer partials -> X1 -------
-  const int NQ = net == 0 ? 3 : 1;
-  {
-    float ps[12];
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-      const float h = tanh_f32(acc[0][0][q4] + b2v);
-      acc[0][0][q4] = h;
-#pragma unroll
-      for (int q = 0; q < 3; ++q) ps[q * 4 + q4] = fmaf(h, w3[q], 0.0f);
-    }
-    if (NQ == 3) {
-      row16_sum_n<12>(ps);
-    } else {
-      float p0[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) p0[k] = ps[k];
-      row16_sum_n<4>(p0);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ps[k] = p0[k];
-    }
-    if (li == 0) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        if (q >= NQ) break;
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) sm.xs[4 * lg + q4][q][w] = ps[q * 4 + q4];
-      }
-    }
-  }
+  fc2_out_partials(acc, b2v, w3, net, li, lg, sm.xs, w);
   PHASE_PROBE(3);
   rp_barrier();
   static_assert(sizeof(sm.xs) == 96 * 8, "X1 staging: 96 8-B stores, six 128-B lines");
@@ -1448,111 +1465,16 @@ __global__ void __launch_bounds__(kCsWaves * 64) rowpass_cs_kernel(
   }
   rp_barrier();
   PHASE_PROBE(13);
-  // ---- C: the loss head (rowpass_kernel's, in every quarter; quarter 0 stores) --
+  // ---- C: the loss head, in every quarter; quarter 0 stores ---------------------
   float* tp = ptail + (int64_t)rb * L.tail;
-  if (tid < R) {
-    const int r = tid, row = r0 + r;
-    float dz[4] = {0.f, 0.f, 0.f, 0.f}, dls[4] = {0.f, 0.f, 0.f, 0.f};
-    if (row < mb) {
-      const float inv = inv_mb;
-      if (net == 0) {
-        float th[3], mu[3], dv[3], var[3], logp[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          th[d] = tanh_f32(out_sum<H / 16>(sm.osum, r, d) + sm.hb3s[d]);
-          mu[d] = max_action * th[d];
-          var[d] = sm.hcs[0][d];
-          dv[d] = sm.ax[r][d] - mu[d];
-          logp[d] = (-(dv[d] * dv[d]) / (2.0f * var[d]) - sm.hcs[1][d]) - kLogSqrt2Pi;
-        }
-        const float lsum = (logp[0] + logp[1]) + logp[2];
-        const float lold = (sm.ax[r][3] + sm.ax[r][4]) + sm.ax[r][5];
-        const float ratio = expf(lsum - lold);
-        if (ratio_out != nullptr && j == 0) ratio_out[row] = ratio;
-        const float adv = sm.ax[r][6];
-        const float s1 = ratio * adv;
-        const float cr = fminf(fmaxf(ratio, 1.0f - epsilon), 1.0f + epsilon);
-        const float s2 = cr * adv;
-        const float g1 = s1 < s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-        const float g2 = s2 < s1 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-        const float inside = (ratio >= 1.0f - epsilon && ratio <= 1.0f + epsilon) ? 1.0f : 0.0f;
-        const float dmin = -inv;
-        const float dratio = dmin * g1 * adv + dmin * g2 * adv * inside;
-        const float dlsum = dratio * ratio;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          const float dvv = dv[d] * sm.hcs[2][d];
-          const float dmu = dlsum * dvv;
-          dz[d] = (dmu * max_action) * (1.0f - th[d] * th[d]);
-          dls[d] = dlsum * (dv[d] * dvv - 1.0f) - ent_coef * inv;
-        }
-      } else {
-        const float vc = out_sum<H / 16>(sm.osum, r, 0) + sm.hb3s[3];
-        dz[3] = 2.0f * inv * (vc - sm.ax[r][7]);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sm.dz3s[r][q] = dz[q];
-    float red[7] = {dz[0], dz[1], dz[2], dls[0], dls[1], dls[2], dz[3]};
-    row16_sum_n<7>(red);
-    if (r == 0 && j == 0) {
-      if (net == 0) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          tp[5 * H + q] = red[q];
-          tp[5 * H + 4 + q] = red[3 + q];
-        }
-        tp[5 * H + 3] = 0.0f;
-        tp[5 * H + 7] = 0.0f;
-      } else {
-        tp[6 * H + 8] = red[6];
-        tp[6 * H + 9] = 0.0f; tp[6 * H + 10] = 0.0f; tp[6 * H + 11] = 0.0f;
-      }
-    }
-  }
+  loss_head<H, R, false>(mb, r0, net, inv_mb, epsilon, ent_coef, max_action, sm.osum, sm.hcs, sm.hb3s, sm.ax, sm.dz3s,
+                         tp, nullptr, j == 0);
   rp_barrier();
   PHASE_PROBE(4);
-  // ---- C: tail of this tile (rowpass_kernel's), dZ2 planes -> LDS, k-packed, X2 --
+  // ---- C: tail of this tile, dZ2 planes -> LDS, k-packed, X2 -------------------
   float d2v[1][1][4];
   unsigned d2w[1][1][6];
-  auto tail = [&](auto actor) {
-    constexpr bool ACT = decltype(actor)::value;
-    constexpr int NC = ACT ? 3 : 1;
-    const int n = n0 + li;
-    float cb2 = 0.f, cw[NC];
-#pragma unroll
-    for (int q = 0; q < NC; ++q) cw[q] = 0.f;
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-      const int r = 4 * lg + q4;
-      const float h = acc[0][0][q4];
-      float dh;
-      if constexpr (ACT) dh = (sm.dz3s[r][0] * w3[0] + sm.dz3s[r][1] * w3[1]) + sm.dz3s[r][2] * w3[2];
-      else dh = sm.dz3s[r][3] * w3[0];
-      const float d2 = dh * (1.0f - h * h);
-      d2v[0][0][q4] = d2;
-      cb2 += d2;
-      if constexpr (ACT) {
-        cw[0] = fmaf(sm.dz3s[r][0], h, cw[0]); cw[1] = fmaf(sm.dz3s[r][1], h, cw[1]); cw[2] = fmaf(sm.dz3s[r][2], h, cw[2]);
-      } else {
-        cw[0] = fmaf(sm.dz3s[r][3], h, cw[0]);
-      }
-    }
-    put3_col4<PS, LDP>(sm.dzp, (4 * lg) * LDP + n, d2v[0][0], d2w[0][0]);
-    cb2 = xor32_sum(xor16_sum(cb2));
-#pragma unroll
-    for (int q = 0; q < NC; ++q) cw[q] = xor32_sum(xor16_sum(cw[q]));
-    if (lg == 0) {
-      tp[net * H + n] = cb2;
-      if constexpr (ACT) {
-        tp[2 * H + n] = cw[0]; tp[3 * H + n] = cw[1]; tp[4 * H + n] = cw[2];
-      } else {
-        tp[5 * H + 8 + n] = cw[0];
-      }
-    }
-  };
-  if (net == 0) tail(std::true_type{});
-  else tail(std::false_type{});
+  tail<H, 1, 1, LDP, PS>(acc, w3, sm.dz3s, nullptr, sm.dzp, d2v, d2w, tp, net, n0);
   store_kx_w<H, R, 1, true>(dZ2x + net * 3 * PLX, PLX, r0, n0, d2w);
   rp_barrier();
   PHASE_PROBE(5);
@@ -1584,21 +1506,8 @@ __global__ void __launch_bounds__(kCsWaves * 64) rowpass_cs_kernel(
   acc[0][0] = f4{0.f, 0.f, 0.f, 0.f};
   mfma_rows3<H, LDP, PS, H, 1, 1, true>(sm.dzp, W2T + (int64_t)net * H * H, n0, acc, &preD);
   PHASE_PROBE(6);
-  // ---- E: dZ1, [dW1 | db1] rows of this tile (rowpass_kernel's) ---------------
-  float* pw = pw1 + (int64_t)rb * 2 * H * 20 + (int64_t)net * H * 20;
-#pragma unroll
-  for (int q4 = 0; q4 < 4; ++q4) acc[0][0][q4] = acc[0][0][q4] * (1.0f - h1[0][0][q4] * h1[0][0][q4]);
-#pragma unroll
-  for (int hb = 0; hb < 2; ++hb) {
-    f4 d = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) d = mfma4(acc[0][0][kk], sm.S[4 * lg + kk][16 * hb + li], d);
-    const int kp = 16 * hb + li;
-    if (kp < 20) {
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) pw[(int64_t)(n0 + 4 * lg + q4) * 20 + kp] = d[q4];
-    }
-  }
+  // ---- E: dZ1, [dW1 | db1] rows of this tile ----------------------------------
+  phase_e(acc, h1, sm.S, pw1 + (int64_t)rb * 2 * H * 20 + (int64_t)net * H * 20, n0);
   PHASE_PROBE(7);
   if constexpr (SPAN) satrl_span::exit(span, span_t0);
 }
@@ -2423,6 +2332,34 @@ bool kx_fits(int H, int mb, int net, int64_t kx_elems, const char* who) {
     if (e_ != hipSuccess) { g_err = hipGetErrorString(e_); return -2; }     \
   } while (0)
 
+// One launch of a span-probed kernel (span_probe.h): its measurement
+// instantiation (SPAN = true) when the probe handed this launch a span `sp`,
+// else the plain one; `sp` is the kernel's last argument either way.
+template <class... KA, class... A>
+void launch_span(void (*probed)(KA...), void (*plain)(KA...), unsigned long long* sp, dim3 grid, dim3 block,
+                 void* stream, A... args) {
+  void (*const k)(KA...) = sp ? probed : plain;
+  hipLaunchKernelGGL(k, grid, block, 0, (hipStream_t)stream, args..., sp);
+}
+// policy_kernel<H, NW, MODE> at width H on grid g, probed as span kind `kind`
+template <int MODE, class... A>
+void launch_policy(int H, int kind, dim3 g, void* stream, A... args) {
+  const int nw = H == 64 ? 4 : H == 128 ? 8 : kPolNW;
+  unsigned long long* sp = satrl_span::take(kind, (int64_t)g.x * nw);
+  if (H == 64)
+    launch_span(policy_kernel<64, 4, MODE, true>, policy_kernel<64, 4, MODE>, sp, g, dim3(nw * 64), stream, args...);
+  else if (H == 128)
+    launch_span(policy_kernel<128, 8, MODE, true>, policy_kernel<128, 8, MODE>, sp, g, dim3(nw * 64), stream, args...);
+  else
+    launch_span(policy_kernel<256, kPolNW, MODE, true>, policy_kernel<256, kPolNW, MODE>, sp, g, dim3(nw * 64), stream,
+                args...);
+}
+// the two instantiations of a rowpass_kernel, {probed, plain}
+template <int H, int NW, int R, bool FDW2, bool KX>
+auto rowpass_k() {
+  return std::make_pair(rowpass_kernel<H, NW, R, FDW2, KX, true>, rowpass_kernel<H, NW, R, FDW2, KX>);
+}
+
 // ---------------------------------------------------------------------------
 // peer_allreduce: the data-parallel gradient all-reduce of G over the W ranks
 // of one node without RCCL, fused with reduce_dp (G /= W, the per-block
@@ -2666,7 +2603,6 @@ static int launch_rowpass(int H, int mb, int net, const float* src, const int64_
                           bool kx = false) {
   const int R = rows_per_wg(H, mb), nrb = n_head_wg(H, mb);
   dim3 g((net < 0 ? 2 : 1) * nrb);   // (row block, net) pairs, or row blocks of one net
-  hipStream_t s = (hipStream_t)stream;
   // waves per workgroup: one 16-column tile per wave for both 16-row tiles
   const float inv_mb = 1.0f / (float)mb;
   const int nw = H == 64 ? 4 : H == 128 ? 8 : 16;                  // waves per workgroup
@@ -2676,41 +2612,30 @@ static int launch_rowpass(int H, int mb, int net, const float* src, const int64_
   const dim3 gc((unsigned)((2 * nrb + 7) / 8 * 32));
   unsigned long long* sp =
       satrl_span::take(satrl_span::kRowpass, cs ? (int64_t)gc.x * kCsWaves : (int64_t)g.x * nw);
-#define RP_ARGS mb, src, idx, P, W2X, epsilon, ent_coef, max_action, H1, dZ2, ptail, pw1, net, p2, nrb, ratio, inv_mb, sp
-#define RP_LAUNCH(HH, NWW, RR, F, K)                                                                          \
-  do {                                                                                                        \
-    if (sp) hipLaunchKernelGGL((rowpass_kernel<HH, NWW, RR, F, K, true>), g, dim3(NWW * 64), 0, s, RP_ARGS);  \
-    else hipLaunchKernelGGL((rowpass_kernel<HH, NWW, RR, F, K>), g, dim3(NWW * 64), 0, s, RP_ARGS);           \
-  } while (0)
+  auto rp = [&](auto k) {
+    launch_span(k.first, k.second, sp, g, dim3(nw * 64), stream, mb, src, idx, P, W2X, epsilon, ent_coef, max_action,
+                H1, dZ2, ptail, pw1, net, p2, nrb, ratio, inv_mb);
+  };
   if (H == 64 && fdw2)
-    RP_LAUNCH(64, 4, kRows, true, false);
+    rp(rowpass_k<64, 4, kRows, true, false>());
   else if (H == 64)
-    RP_LAUNCH(64, 4, kRows, false, false);
+    rp(rowpass_k<64, 4, kRows, false, false>());
   else if (H == 128 && fdw2)
-    RP_LAUNCH(128, 8, kRows, true, false);
+    rp(rowpass_k<128, 8, kRows, true, false>());
   else if (H == 128)
-    RP_LAUNCH(128, 8, kRows, false, false);
-  else if (cs) {
-    if (sp)
-      hipLaunchKernelGGL(rowpass_cs_kernel<true>, gc, dim3(kCsWaves * 64), 0, s, mb, src, idx, P,
-                         static_cast<const float*>(W2X), epsilon, ent_coef, max_action,
-                         reinterpret_cast<unsigned short*>(H1), reinterpret_cast<unsigned short*>(dZ2), ptail, pw1,
-                         ratio, inv_mb, sp);
-    else
-      hipLaunchKernelGGL(rowpass_cs_kernel<false>, gc, dim3(kCsWaves * 64), 0, s, mb, src, idx, P,
-                         static_cast<const float*>(W2X), epsilon, ent_coef, max_action,
-                         reinterpret_cast<unsigned short*>(H1), reinterpret_cast<unsigned short*>(dZ2), ptail, pw1,
-                         ratio, inv_mb, nullptr);
-  } else if (kx && R == kRowsShort)
-    RP_LAUNCH(256, 16, kRowsShort, false, true);
+    rp(rowpass_k<128, 8, kRows, false, false>());
+  else if (cs)
+    launch_span(rowpass_cs_kernel<true>, rowpass_cs_kernel<false>, sp, gc, dim3(kCsWaves * 64), stream, mb, src, idx, P,
+                static_cast<const float*>(W2X), epsilon, ent_coef, max_action, reinterpret_cast<unsigned short*>(H1),
+                reinterpret_cast<unsigned short*>(dZ2), ptail, pw1, inv_mb);
+  else if (kx && R == kRowsShort)
+    rp(rowpass_k<256, 16, kRowsShort, false, true>());
   else if (kx)
-    RP_LAUNCH(256, kNW256, kRows, false, true);
+    rp(rowpass_k<256, kNW256, kRows, false, true>());
   else if (R == kRowsShort)
-    RP_LAUNCH(256, 16, kRowsShort, false, false);
+    rp(rowpass_k<256, 16, kRowsShort, false, false>());
   else
-    RP_LAUNCH(256, kNW256, kRows, false, false);
-#undef RP_LAUNCH
-#undef RP_ARGS
+    rp(rowpass_k<256, kNW256, kRows, false, false>());
   LAUNCH_CHECK();
   return 0;
 }
@@ -2841,12 +2766,8 @@ int satrl_ppo_dw2_kx(int H, int mb, int net, int S, const void* H1x, const void*
     return -1;
   const dim3 g((unsigned)((net < 0 ? 2 : 1) * (256 / kKxTW) * (256 / kKxTW) * S));
   unsigned long long* sp = satrl_span::take(satrl_span::kDw2, (int64_t)g.x * 4);
-  if (sp)
-    hipLaunchKernelGGL((dw2_kx_kernel<kKxTW, true>), g, dim3(256), 0, (hipStream_t)stream, mb, S, cps * 32, net,
-                       static_cast<const unsigned short*>(H1x), static_cast<const unsigned short*>(dZ2x), p2, sp);
-  else
-    hipLaunchKernelGGL((dw2_kx_kernel<kKxTW>), g, dim3(256), 0, (hipStream_t)stream, mb, S, cps * 32, net,
-                       static_cast<const unsigned short*>(H1x), static_cast<const unsigned short*>(dZ2x), p2, sp);
+  launch_span(dw2_kx_kernel<kKxTW, true>, dw2_kx_kernel<kKxTW>, sp, g, dim3(256), stream, mb, S, cps * 32, net,
+              static_cast<const unsigned short*>(H1x), static_cast<const unsigned short*>(dZ2x), p2);
   LAUNCH_CHECK();
   return 0;
 }
@@ -2865,12 +2786,8 @@ int satrl_ppo_dw2_kx_w1(int H, int mb, int net, int S, const void* H1x, const vo
   const dim3 g((unsigned)(ndw + rg.nb1 + rg.nbt));
   unsigned long long* sp = satrl_span::take(satrl_span::kDw2, (int64_t)g.x * 4);
   const unsigned short *h1 = static_cast<const unsigned short*>(H1x), *dz = static_cast<const unsigned short*>(dZ2x);
-  if (sp)
-    hipLaunchKernelGGL((dw2_kx_w1_kernel<kKxTW, true>), g, dim3(256), 0, (hipStream_t)stream, mb, S, cps * 32, net, h1,
-                       dz, p2, ndw, rg, mode, p1, pt, G, nsq, sp);
-  else
-    hipLaunchKernelGGL((dw2_kx_w1_kernel<kKxTW>), g, dim3(256), 0, (hipStream_t)stream, mb, S, cps * 32, net, h1, dz,
-                       p2, ndw, rg, mode, p1, pt, G, nsq, sp);
+  launch_span(dw2_kx_w1_kernel<kKxTW, true>, dw2_kx_w1_kernel<kKxTW>, sp, g, dim3(256), stream, mb, S, cps * 32, net,
+              h1, dz, p2, ndw, rg, mode, p1, pt, G, nsq);
   LAUNCH_CHECK();
   return 0;
 }
@@ -2911,12 +2828,8 @@ int satrl_ppo_reduce(int H, int mb, int net, int S, int mode, const float* p2, i
   const RedGeom g = geom(H, mb, S, net);
   const int nb = w2_only ? g.nb2 : n_blocks(g);
   unsigned long long* sp = satrl_span::take(satrl_span::kReduce, (int64_t)nb * 4);
-  if (sp)
-    hipLaunchKernelGGL(reduce_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, H, g, mode, p2, p1, pt, G,
-                       nsq, steps, 1, sp);
-  else
-    hipLaunchKernelGGL(reduce_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, H, g, mode, p2, p1, pt, G,
-                       nsq, steps, 1, sp);
+  launch_span(reduce_kernel<true>, reduce_kernel<false>, sp, dim3(nb), dim3(256), stream, H, g, mode, p2, p1, pt, G,
+              nsq, steps, 1);
   LAUNCH_CHECK();
   return 0;
 }
@@ -3040,12 +2953,8 @@ int satrl_ppo_adam(int H, int mb, int net, const double* nsq, const double* step
     return -1;
   const int nblk = n_blocks(geom(H, mb, 1, net));
   unsigned long long* sp = satrl_span::take(satrl_span::kAdam, (int64_t)n_adam_blocks(H, net) * 4);
-  if (sp)
-    hipLaunchKernelGGL(adam_kernel<true>, dim3(n_adam_blocks(H, net)), dim3(256), 0, (hipStream_t)stream, H, nblk,
-                       nsq, steps, bct, bct_len, lr, beta1, beta2, eps, max_norm, use_clip, G, P, M, V, W2X, net, sp);
-  else
-    hipLaunchKernelGGL(adam_kernel<false>, dim3(n_adam_blocks(H, net)), dim3(256), 0, (hipStream_t)stream, H, nblk,
-                       nsq, steps, bct, bct_len, lr, beta1, beta2, eps, max_norm, use_clip, G, P, M, V, W2X, net, sp);
+  launch_span(adam_kernel<true>, adam_kernel<false>, sp, dim3(n_adam_blocks(H, net)), dim3(256), stream, H, nblk, nsq,
+              steps, bct, bct_len, lr, beta1, beta2, eps, max_norm, use_clip, G, P, M, V, W2X, net);
   LAUNCH_CHECK();
   return 0;
 }
@@ -3086,50 +2995,18 @@ int satrl_policy_act(int H, int64_t N, const float* obs, const float* P0, const 
   uint32_t k00, k01, k10, k11;
   philox_key(seed, 0, k00, k01);
   philox_key(seed, 1, k10, k11);
-  const dim3 g((unsigned)(nag * ((N + kPolRows - 1) / kPolRows)));
-  hipStream_t s = (hipStream_t)stream;
-  const int nw = H == 64 ? 4 : H == 128 ? 8 : kPolNW;
-  unsigned long long* sp = satrl_span::take(satrl_span::kPolicyAct, (int64_t)g.x * nw);
-#define POL_ARGS N, obs, P0, P1, nag, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, logp0, act1, \
-                 logp1, nullptr, sp
-#define POL_LAUNCH(HH, NWW)                                                                               \
-  do {                                                                                                    \
-    if (sp) hipLaunchKernelGGL((policy_kernel<HH, NWW, 0, true>), g, dim3(NWW * 64), 0, s, POL_ARGS);     \
-    else hipLaunchKernelGGL((policy_kernel<HH, NWW, 0>), g, dim3(NWW * 64), 0, s, POL_ARGS);              \
-  } while (0)
-  if (H == 64)
-    POL_LAUNCH(64, 4);
-  else if (H == 128)
-    POL_LAUNCH(128, 8);
-  else
-    POL_LAUNCH(256, kPolNW);
-#undef POL_LAUNCH
-#undef POL_ARGS
+  launch_policy<0>(H, satrl_span::kPolicyAct, dim3((unsigned)(nag * ((N + kPolRows - 1) / kPolRows))), stream, N, obs,
+                   P0, P1, nag, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, logp0, act1, logp1,
+                   nullptr);
   LAUNCH_CHECK();
   return 0;
 }
 
 int satrl_policy_value(int H, int64_t N, const float* obs, const float* P, float* v_out, void* stream) {
   if (!valid_h(H) || N <= 0 || !obs || !P || !v_out) return -1;
-  const dim3 g((unsigned)((N + kPolRows - 1) / kPolRows));
-  hipStream_t s = (hipStream_t)stream;
-  const int nw = H == 64 ? 4 : H == 128 ? 8 : kPolNW;
-  unsigned long long* sp = satrl_span::take(satrl_span::kPolicyValue, (int64_t)g.x * nw);
-#define VAL_ARGS N, obs, P, nullptr, 1, 0.0f, 0u, 0u, 0u, 0u, (int64_t)0, (uint64_t)0, nullptr, nullptr, nullptr, \
-                 nullptr, nullptr, v_out, sp
-#define VAL_LAUNCH(HH, NWW)                                                                               \
-  do {                                                                                                    \
-    if (sp) hipLaunchKernelGGL((policy_kernel<HH, NWW, 1, true>), g, dim3(NWW * 64), 0, s, VAL_ARGS);     \
-    else hipLaunchKernelGGL((policy_kernel<HH, NWW, 1>), g, dim3(NWW * 64), 0, s, VAL_ARGS);              \
-  } while (0)
-  if (H == 64)
-    VAL_LAUNCH(64, 4);
-  else if (H == 128)
-    VAL_LAUNCH(128, 8);
-  else
-    VAL_LAUNCH(256, kPolNW);
-#undef VAL_LAUNCH
-#undef VAL_ARGS
+  launch_policy<1>(H, satrl_span::kPolicyValue, dim3((unsigned)((N + kPolRows - 1) / kPolRows)), stream, N, obs, P,
+                   nullptr, 1, 0.0f, 0u, 0u, 0u, 0u, (int64_t)0, (uint64_t)0, nullptr, nullptr, nullptr, nullptr,
+                   nullptr, v_out);
   LAUNCH_CHECK();
   return 0;
 }
