@@ -2332,15 +2332,7 @@ bool kx_fits(int H, int mb, int net, int64_t kx_elems, const char* who) {
     if (e_ != hipSuccess) { g_err = hipGetErrorString(e_); return -2; }     \
   } while (0)
 
-// One launch of a span-probed kernel (span_probe.h): its measurement
-// instantiation (SPAN = true) when the probe handed this launch a span `sp`,
-// else the plain one; `sp` is the kernel's last argument either way.
-template <class... KA, class... A>
-void launch_span(void (*probed)(KA...), void (*plain)(KA...), unsigned long long* sp, dim3 grid, dim3 block,
-                 void* stream, A... args) {
-  void (*const k)(KA...) = sp ? probed : plain;
-  hipLaunchKernelGGL(k, grid, block, 0, (hipStream_t)stream, args..., sp);
-}
+using satrl_span::launch_span;
 // policy_kernel<H, NW, MODE> at width H on grid g, probed as span kind `kind`
 template <int MODE, class... A>
 void launch_policy(int H, int kind, dim3 g, void* stream, A... args) {

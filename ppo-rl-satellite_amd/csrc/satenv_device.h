@@ -381,6 +381,7 @@ SATENV_HD_NOINLINE double hybrd1(double A, double st, double dvm, double x) {
 // ---------------------------------------------------------------------------
 // satellite_function.py:462-556 rf_extreme_point('orbit_c1'/'orbit_c2'), fai = 0
 // ---------------------------------------------------------------------------
+constexpr double kDzMu = 3.986e14;                           // Time_window_of_danger_zone default u
 struct Pursuer { double u, dv2, e, f0, p, r, sf0, X, sq; };
 
 // the two fsolve problems of one rf_extreme_point call (guesses +pi/2 and
@@ -426,13 +427,14 @@ SATENV_HD void rf_setup(const Pursuer& P, double f_c, RfSolve& q) {
   }
 }
 
-// rf of one solution alpha (:525-530 / :543-548), before abs and sort
-SATENV_HD double rf_one(const Pursuer& P, const RfSolve& q, double al) {
+// rf of one solution alpha (:525-530 / :543-548), before abs and sort; of
+// the chaser it needs only r (its u is always kDzMu)
+SATENV_HD double rf_one(double r, const RfSolve& q, double al) {
   double sa, ca;
   sincos(al, &sa, &ca);
   const double vx = q.vx0 + q.dvm * ca, vy = q.vy0 + q.dvm * sa;                 // :525-528
-  const double hm = P.r * vy;
-  return pow2(hm) / (P.u * (1.0 - q.ct) + hm * vy * q.ct - hm * vx * q.st);     // :530
+  const double hm = r * vy;
+  return pow2(hm) / (kDzMu * (1.0 - q.ct) + hm * vy * q.ct - hm * vx * q.st);   // :530
 }
 
 // abs and sort of the two rf values (:549-554); (0, 0) when temp1 < 0 (:477)
@@ -447,7 +449,7 @@ SATENV_HD void rf_sort(bool ok, double rf0, double rf1, double& rmax, double& rm
 SATENV_HD void rf_finish(const Pursuer& P, const RfSolve& q, double al0, double al1, double& rmax,
                                           double& rmin) {
   if (!q.ok) { rmax = 0.0; rmin = 0.0; return; }
-  rf_sort(true, rf_one(P, q, al0), rf_one(P, q, al1), rmax, rmin);
+  rf_sort(true, rf_one(P.r, q, al0), rf_one(P.r, q, al1), rmax, rmin);
 }
 
 // self.Delta_V_c ** 2 by numpy scalar type
@@ -468,13 +470,10 @@ SATENV_HD double fuel_sq(double fuel, int mode) {
 // dz_setup / dz_finish, operation for operation.
 struct DzCtx { Pursuer P; RfSolve q[2]; double r_ft1, r_ft2; };
 
-constexpr double kDzMu = 3.986e14;                           // Time_window_of_danger_zone default u
-
-// the chaser's (which = 0) or the target's (1) element set from the relative state
-SATENV_HD int dz_elements(const Params& prm, double X0, double X1, double X2, double V0, double V1, double V2,
-                          Elements& out) {
-  return orbital_elements(kDzMu, prm.R_cw[0] + X0, prm.R_cw[1] + X1, prm.R_cw[2] + X2, prm.V_cw[0] + V0,
-                          prm.V_cw[1] + V1, prm.V_cw[2] + V2, out);
+// the element set of one craft from its relative state x = position[3], velocity[3]
+SATENV_HD int dz_elements(const Params& prm, const double* x, Elements& out) {
+  return orbital_elements(kDzMu, prm.R_cw[0] + x[0], prm.R_cw[1] + x[1], prm.R_cw[2] + x[2], prm.V_cw[0] + x[3],
+                          prm.V_cw[1] + x[4], prm.V_cw[2] + x[5], out);
 }
 
 // Time_window_of_danger_zone attributes of the chaser (:54-58, :82-86)
@@ -522,13 +521,12 @@ SATENV_HD int dz_count(double mx1, double mn1, double mx2, double mn2, double r_
   return (in1 && in2) ? 2 : ((in1 || in2) ? 1 : 0);
 }
 
-SATENV_HD int dz_setup(const Params& prm, double Pp0, double Pp1, double Pp2, double Pv0,
-                                        double Pv1, double Pv2, double Ep0, double Ep1, double Ep2, double Ev0,
-                                        double Ev1, double Ev2, double fuel, int fmode, DzCtx& z) {
+// k = the relative states of chaser and target, Pp Pv Ep Ev
+SATENV_HD int dz_setup(const Params& prm, const double* k, double fuel, int fmode, DzCtx& z) {
   Elements C, T;
-  int rc = dz_elements(prm, Pp0, Pp1, Pp2, Pv0, Pv1, Pv2, C);
+  int rc = dz_elements(prm, k, C);
   if (rc) return rc;
-  rc = dz_elements(prm, Ep0, Ep1, Ep2, Ev0, Ev1, Ev2, T);
+  rc = dz_elements(prm, k + 6, T);
   if (rc) return rc;
   dz_pursuer(C, fuel, fmode, z.P);
   double u_c1, u_c2, u_t1, u_t2;
@@ -548,11 +546,9 @@ SATENV_HD int dz_finish(const DzCtx& z, const double (&al)[4]) {
 }
 
 // the whole count in one lane (the four solves one after another)
-SATENV_HD int danger_zone(const Params& prm, double Pp0, double Pp1, double Pp2, double Pv0,
-                                           double Pv1, double Pv2, double Ep0, double Ep1, double Ep2, double Ev0,
-                                           double Ev1, double Ev2, double fuel, int fmode, int& count) {
+SATENV_HD int danger_zone(const Params& prm, const double* k, double fuel, int fmode, int& count) {
   DzCtx z;
-  const int rc = dz_setup(prm, Pp0, Pp1, Pp2, Pv0, Pv1, Pv2, Ep0, Ep1, Ep2, Ev0, Ev1, Ev2, fuel, fmode, z);
+  const int rc = dz_setup(prm, k, fuel, fmode, z);
   if (rc) return rc;
   double al[4];
 #pragma unroll

@@ -27,12 +27,7 @@ using namespace satenv;
 
 namespace {
 
-
 thread_local std::string g_last_error;
-
-bool params_ok(const satenv_params* p) {
-  return p->propagator >= 0 && p->propagator <= 2 && p->rk4_substeps >= 1;
-}
 
 int fail(int code, const std::string& msg) {
   g_last_error = msg;
@@ -47,7 +42,7 @@ int fail(int code, const std::string& msg) {
 
 #ifdef SATENV_PHASE_PROBE
 // development-only phase stamps of step_kernel_wide (tools/env_phase_probe.py),
-// never in the shipped build: [workgroup][stamp][wave][s_memtime]
+// never in the shipped build: [workgroup][stamp][wave] = clock64()
 __device__ unsigned long long g_env_probe[1024][8][4];
 #define ENV_PROBE(k)                                                                  \
   do {                                                                                \
@@ -59,46 +54,50 @@ __device__ unsigned long long g_env_probe[1024][8][4];
 #endif
 
 // wave-level reduction of the per-step stats, one f64 atomic per wave and counter
-__device__ __forceinline__ void wave_stats(double* stats, double fin, double fin_ret, double rew, double cap) {
+__device__ __forceinline__ void wave_stats(double* stats, StepStats s) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
-    fin += __shfl_xor(fin, off, 64);
-    fin_ret += __shfl_xor(fin_ret, off, 64);
-    rew += __shfl_xor(rew, off, 64);
-    cap += __shfl_xor(cap, off, 64);
+    s.fin += __shfl_xor(s.fin, off, 64);
+    s.fin_ret += __shfl_xor(s.fin_ret, off, 64);
+    s.rew += __shfl_xor(s.rew, off, 64);
+    s.cap += __shfl_xor(s.cap, off, 64);
   }
   if ((threadIdx.x & 63) == 0) {
-    if (fin != 0.0) atomicAdd(stats + 0, fin);
-    if (fin_ret != 0.0) atomicAdd(stats + 1, fin_ret);
-    atomicAdd(stats + 2, rew);
-    if (cap != 0.0) atomicAdd(stats + 3, cap);
+    if (s.fin != 0.0) atomicAdd(stats + 0, s.fin);
+    if (s.fin_ret != 0.0) atomicAdd(stats + 1, s.fin_ret);
+    atomicAdd(stats + 2, s.rew);
+    if (s.cap != 0.0) atomicAdd(stats + 3, s.cap);
   }
 }
 
-// one lane per env, the count's four solves one after another (64-lane blocks)
+// The step kernels share one signature (launch_step); only a SPAN instantiation uses its last argument.
+// One lane per env, the count's four solves one after another (64-lane blocks):
 template <bool AUTORESET, bool RK45 = false>
 __global__ void __launch_bounds__(64) step_kernel(const Params prm, int64_t n, double* __restrict__ f64,
-                                                  int32_t* __restrict__ i32, StepIO io) {
+                                                  int32_t* __restrict__ i32, StepIO io, unsigned long long*) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  double fin = 0.0, fin_ret = 0.0, rew_acc = 0.0, cap = 0.0;
+  StepStats s;
   if (i < n) {
-    Lane L;
-    step_begin<RK45>(prm, n, f64, i32, io, i, AUTORESET, L);
-    if (L.err) atomicCAS(io.err, 0, L.err);
-    cap = L.cap;
-    if (!L.terminal) {
-      int cnt = 0;
-      const int rc = danger_zone(prm, L.k[0], L.k[1], L.k[2], L.k[3], L.k[4], L.k[5], L.k[6], L.k[7], L.k[8],
-                                 L.k[9], L.k[10], L.k[11], L.fuel_c, L.fcm, cnt);   // :150, :317-332
-      if (rc) atomicCAS(io.err, 0, rc);
-      step_reward(prm, L, cnt);
-    }
-    step_end(prm, n, f64, i32, io, i, AUTORESET, L, fin, fin_ret, rew_acc);
+    const int rc = step_lane<RK45>(prm, n, f64, i32, io, i, AUTORESET, s);
+    if (rc) atomicCAS(io.err, 0, rc);
   }
-  if (io.stats) wave_stats(io.stats, fin, fin_ret, rew_acc, cap);
+  if (io.stats) wave_stats(io.stats, s);
 }
 
-// 64 envs per 4-wave workgroup: wave 0 runs the env lanes (step_begin, the
+// Head of an env lane of the multi-wave kernels (wave 0): step_lane up to the
+// count, which is their schedule.  Returns whether the step needs the count.
+// (Their tail stays spelled out, `if (!L.terminal) { count, reward } step_end`:
+// a shared lane_tail cost the wide kernel time, EXPERIMENTS.md.)
+template <bool RK45>
+__device__ __forceinline__ bool lane_head(const Params& prm, int64_t n, const double* __restrict__ f64,
+                                          const int32_t* __restrict__ i32, const StepIO& io, int64_t i,
+                                          bool autoreset, Lane& L, StepStats& s) {
+  step_begin<RK45>(prm, n, f64, i32, io, i, autoreset, L, s);
+  if (L.err) atomicCAS(io.err, 0, L.err);
+  return !L.terminal;
+}
+
+// 64 envs per 4-wave workgroup: wave 0 runs the env lanes (lane_head, the
 // count's set-up, then its finish and step_end), and between two barriers
 // wave w solves fsolve problem w of every env of the block (the c-th
 // rf_extreme_point's k-th guess, w = 2c + k) -- so the four dependent
@@ -109,7 +108,7 @@ __global__ void __launch_bounds__(64) step_kernel(const Params prm, int64_t n, d
 constexpr int kSplitEnvs = 64;
 template <bool AUTORESET, bool RK45 = false>
 __global__ void __launch_bounds__(256) step_kernel_split(const Params prm, int64_t n, double* __restrict__ f64,
-                                                         int32_t* __restrict__ i32, StepIO io) {
+                                                         int32_t* __restrict__ i32, StepIO io, unsigned long long*) {
   __shared__ double sA[4][kSplitEnvs], sSt[4][kSplitEnvs], sDvm[4][kSplitEnvs], sX[4][kSplitEnvs];
   __shared__ int sOn[4][kSplitEnvs];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -118,15 +117,12 @@ __global__ void __launch_bounds__(256) step_kernel_split(const Params prm, int64
   Lane L;
   DzCtx z;
   int rc = 0;
-  double fin = 0.0, fin_ret = 0.0, rew_acc = 0.0, cap = 0.0;
+  StepStats s;
   if (w == 0) {
     bool on[2] = {false, false};
     if (live) {
-      step_begin<RK45>(prm, n, f64, i32, io, i, AUTORESET, L);
-      if (L.err) atomicCAS(io.err, 0, L.err);
-      cap = L.cap;
-      if (!L.terminal) {
-        rc = lane_setup(prm, L, z);                                      // :150, :317-332
+      if (lane_head<RK45>(prm, n, f64, i32, io, i, AUTORESET, L, s)) {
+        rc = dz_setup(prm, L.k, L.fuel_c, L.fcm, z);                     // :150, :317-332
         if (rc == 0) { on[0] = z.q[0].ok; on[1] = z.q[1].ok; }
       }
     }
@@ -158,15 +154,15 @@ __global__ void __launch_bounds__(256) step_kernel_split(const Params prm, int64
       }
       step_reward(prm, L, cnt);
     }
-    step_end(prm, n, f64, i32, io, i, AUTORESET, L, fin, fin_ret, rew_acc);
+    step_end(prm, n, f64, i32, io, i, AUTORESET, L, s);
   }
-  if (w == 0 && io.stats) wave_stats(io.stats, fin, fin_ret, rew_acc, cap);
+  if (w == 0 && io.stats) wave_stats(io.stats, s);
 }
 
 // 64 envs per 4-wave workgroup with the whole per-env chain spread over the
 // waves, not only the four solves (step_kernel_split keeps the rest of the
 // chain in wave 0).  Between barriers, per env:
-//   I   wave 0: step_begin (state, actions, fuel, propagation, terminal tests)
+//   I   wave 0: lane_head (state, actions, fuel, propagation, terminal tests)
 //   II  wave 0: chaser elements | wave 1: target elements | wave 2: the
 //       count-independent reward terms (three cosine similarities, pv4)
 //   II' wave 0 also: the chaser's set-up (dz_pursuer) for both waves of III
@@ -180,6 +176,8 @@ __global__ void __launch_bounds__(256) step_kernel_split(const Params prm, int64
 // bit-identical to step_kernel_split (and to the host build where the libm
 // agrees); only the schedule differs.  Phases II-IV each shorten wave 0's
 // dependent FP64 chain (OCML acos/atan/sincos latency) by running next to it.
+// The structs cross waves through the put_* / get_* helpers below: a phase
+// names what it passes on, never a slot number.
 template <int E>
 struct WideSmem {
   double k[12][E];          // state after the propagation
@@ -190,8 +188,8 @@ struct WideSmem {
   double C[6][E], T[6][E];
   int rc[2][E];
   double rt[4][E];          // reward terms
-  double P[9][E];                    // the chaser's Pursuer set-up (dz_pursuer), from phase II
-  double qA[4][E], qAg[4][E], qSt[2][E], qCt[2][E], qDvm[2][E],
+  struct { double u[E], dv2[E], e[E], f0[E], p[E], r[E], sf0[E], X[E], sq[E]; } P;   // dz_pursuer, from phase II
+  double qA[4][E], qAg[4][E], qSt[2][E], qCt[2][E], qDvm[2][E],     // rf_setup c: problems 2c, 2c + 1
       qVx0[2][E], qVy0[2][E];
   int qOk[2][E];
   double rft[2][E];
@@ -210,6 +208,42 @@ __device__ __forceinline__ Elements get_elements(const double (*src)[E], int lan
   el.omega = src[3][lane]; el.Omega = src[4][lane]; el.f = src[5][lane];
   return el;
 }
+// phase II -> III
+template <int E>
+__device__ __forceinline__ void put_pursuer(WideSmem<E>& sm, int lane, const Pursuer& P) {
+  sm.P.u[lane] = P.u; sm.P.dv2[lane] = P.dv2; sm.P.e[lane] = P.e; sm.P.f0[lane] = P.f0;
+  sm.P.p[lane] = P.p; sm.P.r[lane] = P.r; sm.P.sf0[lane] = P.sf0; sm.P.X[lane] = P.X;
+  sm.P.sq[lane] = P.sq;
+}
+template <int E>
+__device__ __forceinline__ Pursuer get_pursuer(const WideSmem<E>& sm, int lane) {
+  Pursuer P;
+  P.u = sm.P.u[lane]; P.dv2 = sm.P.dv2[lane]; P.e = sm.P.e[lane]; P.f0 = sm.P.f0[lane];
+  P.p = sm.P.p[lane]; P.r = sm.P.r[lane]; P.sf0 = sm.P.sf0[lane]; P.X = sm.P.X[lane];
+  P.sq = sm.P.sq[lane];
+  return P;
+}
+// phase III -> IV: rf_extreme_point c's set-up, then problem w = 2c + k of it
+// (q without the A / ag pairs: the wave's own come back as scalars)
+template <int E>
+__device__ __forceinline__ void put_rf(WideSmem<E>& sm, int c, int lane, const RfSolve& q) {
+  sm.qOk[c][lane] = q.ok ? 1 : 0;
+  sm.qA[2 * c][lane] = q.A[0]; sm.qA[2 * c + 1][lane] = q.A[1];
+  sm.qAg[2 * c][lane] = q.ag[0]; sm.qAg[2 * c + 1][lane] = q.ag[1];
+  sm.qSt[c][lane] = q.st; sm.qCt[c][lane] = q.ct; sm.qDvm[c][lane] = q.dvm;
+  sm.qVx0[c][lane] = q.vx0; sm.qVy0[c][lane] = q.vy0;
+}
+template <int E>
+__device__ __forceinline__ RfSolve get_rf_problem(const WideSmem<E>& sm, int w, int lane, double& A, double& ag) {
+  const int c = w >> 1;
+  RfSolve q;
+  q.ok = true;
+  q.st = sm.qSt[c][lane]; q.ct = sm.qCt[c][lane]; q.dvm = sm.qDvm[c][lane];
+  q.vx0 = sm.qVx0[c][lane]; q.vy0 = sm.qVy0[c][lane];
+  A = sm.qA[w][lane];
+  ag = sm.qAg[w][lane];
+  return q;
+}
 
 // ENVS envs per workgroup (lanes >= ENVS of each wave idle): fewer envs per
 // wave put more waves, i.e. more independent dependency chains, on each SIMD
@@ -225,18 +259,15 @@ __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_
   const int64_t i = (int64_t)blockIdx.x * ENVS + lane;
   const bool in_range = env_lane && i < n;
   Lane L;
-  double fin = 0.0, fin_ret = 0.0, rew_acc = 0.0, cap = 0.0;
+  StepStats s;
   ENV_PROBE(0);
   // ---- I -------------------------------------------------------------------
   if (w == 0) {
     int live = 0;
     if (in_range) {
-      step_begin(prm, n, f64, i32, io, i, AUTORESET, L);
-      if (L.err) atomicCAS(io.err, 0, L.err);
-      cap = L.cap;
-      live = L.terminal ? 0 : (1 | (L.p_zero ? 2 : 0));
+      live = lane_head<false>(prm, n, f64, i32, io, i, AUTORESET, L, s) ? (1 | (L.p_zero ? 2 : 0)) : 0;
 #pragma unroll
-      for (int c = 0; c < 12; ++c) sm.k[c][lane] = L.k[c];
+      for (int c = 0; c < 12; ++c) sm.k[c][lane] = L.k[c];     // (no put_lane(L) helper: EXPERIMENTS.md)
 #pragma unroll
       for (int c = 0; c < 3; ++c) sm.pa[c][lane] = L.pa[c];
       sm.fuel[lane] = L.fuel_c;
@@ -249,19 +280,18 @@ __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_
   const int live = env_lane ? sm.live[lane] : 0;
   // ---- II ------------------------------------------------------------------
   if (live & 1) {
-    if (w <= 1) {
+    if (w <= 1) {                                             // chaser: Pp/Pv, target: Ep/Ev
+      double x[6];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) x[c] = sm.k[6 * w + c][lane];
       Elements E;
-      const int o = 6 * w;                                    // chaser: Pp/Pv, target: Ep/Ev
-      const int rc = dz_elements(prm, sm.k[o][lane], sm.k[o + 1][lane], sm.k[o + 2][lane], sm.k[o + 3][lane],
-                                 sm.k[o + 4][lane], sm.k[o + 5][lane], E);
+      const int rc = dz_elements(prm, x, E);
       put_elements<ENVS>(w == 0 ? sm.C : sm.T, lane, E);
       sm.rc[w][lane] = rc;
       if (w == 0 && rc == 0) {                                  // the chaser's set-up, off phase III's path
         Pursuer P;
         dz_pursuer(E, sm.fuel[lane], sm.fcm[lane], P);
-        sm.P[0][lane] = P.u; sm.P[1][lane] = P.dv2; sm.P[2][lane] = P.e; sm.P[3][lane] = P.f0;
-        sm.P[4][lane] = P.p; sm.P[5][lane] = P.r; sm.P[6][lane] = P.sf0; sm.P[7][lane] = P.X;
-        sm.P[8][lane] = P.sq;
+        put_pursuer(sm, lane, P);
       }
     } else if (w == 2) {
       double k[12], t[4];
@@ -284,17 +314,9 @@ __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_
     double u_c1, u_c2, u_t1, u_t2;
     dz_lat(C, T, u_c1, u_c2, u_t1, u_t2);
     if (w <= 1) {
-      Pursuer P;
-      P.u = sm.P[0][lane]; P.dv2 = sm.P[1][lane]; P.e = sm.P[2][lane]; P.f0 = sm.P[3][lane];
-      P.p = sm.P[4][lane]; P.r = sm.P[5][lane]; P.sf0 = sm.P[6][lane]; P.X = sm.P[7][lane];
-      P.sq = sm.P[8][lane];
       RfSolve q;
-      rf_setup(P, (w == 0 ? u_c1 : u_c2) - C.omega, q);         // rf_extreme_point('orbit_c1' / 'orbit_c2')
-      sm.qOk[w][lane] = q.ok ? 1 : 0;
-      sm.qA[2 * w][lane] = q.A[0]; sm.qA[2 * w + 1][lane] = q.A[1];
-      sm.qAg[2 * w][lane] = q.ag[0]; sm.qAg[2 * w + 1][lane] = q.ag[1];
-      sm.qSt[w][lane] = q.st; sm.qCt[w][lane] = q.ct; sm.qDvm[w][lane] = q.dvm;
-      sm.qVx0[w][lane] = q.vx0; sm.qVy0[w][lane] = q.vy0;
+      rf_setup(get_pursuer(sm, lane), (w == 0 ? u_c1 : u_c2) - C.omega, q);   // rf_extreme_point('orbit_c1' / 'orbit_c2')
+      put_rf(sm, w, lane, q);
     } else {
       double r1, r2;
       dz_target_radii(T, u_t1, u_t2, r1, r2);
@@ -305,17 +327,11 @@ __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_
   __syncthreads();
   // ---- IV: problem w = (rf_extreme_point c = w >> 1, guess k = w & 1) ------
   if (ok_el) {
-    const int c = w >> 1;
-    if (sm.qOk[c][lane]) {
-      RfSolve q;
-      q.ok = true;
-      q.st = sm.qSt[c][lane]; q.ct = sm.qCt[c][lane]; q.dvm = sm.qDvm[c][lane];
-      q.vx0 = sm.qVx0[c][lane]; q.vy0 = sm.qVy0[c][lane];
-      const double al = hybrd1(sm.qA[w][lane], q.st, q.dvm, sm.qAg[w][lane]);
-      Pursuer P;
-      P.u = kDzMu;
-      P.r = sm.P[5][lane];
-      sm.rf[w][lane] = rf_one(P, q, al);
+    if (sm.qOk[w >> 1][lane]) {
+      double A, ag;
+      const RfSolve q = get_rf_problem(sm, w, lane, A, ag);
+      const double al = hybrd1(A, q.st, q.dvm, ag);
+      sm.rf[w][lane] = rf_one(sm.P.r[lane], q, al);
     }
   }
   ENV_PROBE(4);
@@ -339,9 +355,9 @@ __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_
       for (int c = 0; c < 4; ++c) t[c] = sm.rt[c][lane];
       step_reward_terms(prm, L, cnt, t);
     }
-    step_end(prm, n, f64, i32, io, i, AUTORESET, L, fin, fin_ret, rew_acc);
+    step_end(prm, n, f64, i32, io, i, AUTORESET, L, s);
   }
-  if (w == 0 && io.stats) wave_stats(io.stats, fin, fin_ret, rew_acc, cap);
+  if (w == 0 && io.stats) wave_stats(io.stats, s);
   ENV_PROBE(6);
   if constexpr (SPAN) satrl_span::exit(span, span_t0);
 }
@@ -350,36 +366,12 @@ __global__ void __launch_bounds__(256) reset_kernel(const Params prm, int64_t n,
                                                     int32_t* __restrict__ i32, int32_t flag, const uint8_t* mask,
                                                     float* obs, double* obs64) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double k[12];
-  const bool hit = mask == nullptr || mask[i] != 0;
-  if (hit) {                                                                // environment.py:66-79
-    reset_kin(prm, k);
-#pragma unroll
-    for (int c = 0; c < 12; ++c) f64[c * n + i] = k[c];
-    const int b = i32[kPlaneBits * n + i];
-    i32[kPlaneBits * n + i] = make_bits(fc_mode(b), ft_mode(b), 1, flag);
-    i32[kPlaneCount * n + i] = 0;
-    f64[kPlaneRet * n + i] = 0.0;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 12; ++c) k[c] = f64[c * n + i];
-  }
-  write_obs(obs, obs64, i, k);
+  if (i < n) reset_env(prm, n, f64, i32, flag, mask, obs, obs64, i);
 }
 
 __global__ void init_kernel(const Params prm, int64_t n, double* f64, int32_t* i32) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-#pragma unroll
-  for (int c = 0; c < 12; ++c) f64[c * n + i] = prm.init_kin[c];           // environment.py:30-33
-  f64[12 * n + i] = prm.fuel_c0;                                            // :42-43
-  f64[13 * n + i] = prm.fuel_t0;
-  f64[14 * n + i] = INFINITY;                                               // :44
-  f64[kPlaneRet * n + i] = 0.0;
-  i32[kPlaneDz * n + i] = 0;                                                // :41
-  i32[kPlaneCount * n + i] = 0;
-  i32[kPlaneBits * n + i] = make_bits(prm.fuel_c0_mode, prm.fuel_t0_mode, 1, prm.flag);
+  if (i < n) init_env(prm, n, f64, i32, i);
 }
 
 __global__ void __launch_bounds__(256) danger_zone_kernel(int64_t n, const double* __restrict__ X,
@@ -389,10 +381,8 @@ __global__ void __launch_bounds__(256) danger_zone_kernel(int64_t n, const doubl
   if (i >= n) return;
   satenv_params prm;
   for (int c = 0; c < 3; ++c) { prm.R_cw[c] = 0.0; prm.V_cw[c] = 0.0; }   // states are already absolute
-  const double* x = X + i * 12;
   int cnt = 0;
-  const int rc = danger_zone(prm, x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], x[9], x[10], x[11],
-                             fuel[i], mode[i], cnt);
+  const int rc = danger_zone(prm, X + i * 12, fuel[i], mode[i], cnt);
   out[i] = rc ? rc : cnt;
 }
 
@@ -558,6 +548,16 @@ __global__ void __launch_bounds__(kRdBlock) rd_kernel(const satenv_rd_orbit* __r
   }
 }
 
+// the element set of env i's pursuer from the state planes (dz_elements:
+// relative_state_to_absolute_state, then the 6-element set with mu 3.986e14)
+__device__ __forceinline__ int pursuer_elements(const Params& prm, int64_t n, const double* __restrict__ f64,
+                                                int64_t i, Elements& E) {
+  double x[6];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) x[c] = f64[c * n + i];
+  return dz_elements(prm, x, E);
+}
+
 // Flag 2: the Incoming_parameters orbit of every env (include/satenv.h
 // satenv_rd_orbits): real_time_data_process.calculate_orbital_elements
 // (:11-105, the same element set as satellite_function's, orbital_elements)
@@ -569,9 +569,7 @@ __global__ void __launch_bounds__(256) rd_orbits_kernel(const Params prm, int64_
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   Elements E;
-  const int rc = orbital_elements(3.986e14, prm.R_cw[0] + f64[0 * n + i], prm.R_cw[1] + f64[1 * n + i],
-                                  prm.R_cw[2] + f64[2 * n + i], prm.V_cw[0] + f64[3 * n + i],
-                                  prm.V_cw[1] + f64[4 * n + i], prm.V_cw[2] + f64[5 * n + i], E);
+  const int rc = pursuer_elements(prm, n, f64, i, E);
   satenv_rd_orbit o;
   o.a = rc ? 0.0 : E.a;                                            // Incoming_parameters :29-33
   o.e0 = rc ? 0.0 : E.e;
@@ -624,10 +622,7 @@ __global__ void __launch_bounds__(surrogate::kThreads) surrogate_kernel(const Pa
         ok = 1;
       } else {
         Elements E;
-        const int rc = orbital_elements(3.986e14, prm.R_cw[0] + f64[0 * n + env], prm.R_cw[1] + f64[1 * n + env],
-                                        prm.R_cw[2] + f64[2 * n + env], prm.V_cw[0] + f64[3 * n + env],
-                                        prm.V_cw[1] + f64[4 * n + env], prm.V_cw[2] + f64[5 * n + env], E);
-        ok = rc == 0;
+        ok = pursuer_elements(prm, n, f64, env, E) == 0;
         // the reference's float32 feature tensor (real_time_data_process.py:117)
         fv[0] = (float)E.a; fv[1] = (float)E.e; fv[2] = (float)E.i; fv[3] = (float)E.f;
         fv[4] = (float)f64[12 * n + env];
@@ -672,49 +667,36 @@ struct satenv_env {
   double* f64 = nullptr;
   int32_t* i32 = nullptr;
   int32_t* err = nullptr;
-  int split = 2;   // step_kernel_wide (2), step_kernel_split (1) or the one-lane step_kernel (0)
-  int wide_envs = 64;
+  int kind = 2;    // step_kernel_wide (2), step_kernel_split (1) or the one-lane step_kernel (0)
+  int wide_envs = 64;   // envs per workgroup of the wide kernel (16 / 32 for A/B; fewer envs per
+                        // workgroup measured no faster)
 };
 
 namespace {
 
 int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
-// envs per workgroup of the wide kernel: 64 (satenv_set_step_kernel: 16 / 32
-// for A/B; fewer envs per workgroup measured no faster)
-int wide_envs(const satenv_env* h) { return h->wide_envs; }
-
 template <bool AR>
 void launch_step(satenv_env* h, const StepIO& io, void* stream) {
-  const dim3 grid(grid_for(h->n, kSplitEnvs));
-  if (h->prm.propagator == 2)   // the RK45 instantiation (its registers stay out of the STM kernels)
-    hipLaunchKernelGGL((step_kernel_split<AR, true>), grid, dim3(256), 0, (hipStream_t)stream, h->prm, h->n, h->f64,
-                       h->i32, io);
-  else if (h->split == 2) {
-    const int envs = wide_envs(h);
-    const dim3 gw(grid_for(h->n, envs));
+  void (*plain)(const Params, int64_t, double*, int32_t*, StepIO, unsigned long long*) = step_kernel<AR>;
+  decltype(plain) probed = nullptr;
+  int envs = 64, threads = 256;   // per workgroup
+  if (h->prm.propagator == 2) {   // the RK45 instantiation (its registers stay out of the STM kernels)
+    plain = step_kernel_split<AR, true>;
+  } else if (h->kind == 2) {
+    envs = h->wide_envs;
+    plain = envs == 16 ? step_kernel_wide<AR, 16> : envs == 32 ? step_kernel_wide<AR, 32> : step_kernel_wide<AR, 64>;
     // the product geometry (64 envs per workgroup) has a SPAN instantiation
     // for the bench's live launch spans (span_probe.h)
-    unsigned long long* sp = envs == 64 ? satrl_span::take(satrl_span::kEnvStep, (int64_t)gw.x * 4) : nullptr;
-    if (envs == 16)
-      hipLaunchKernelGGL((step_kernel_wide<AR, 16>), gw, dim3(256), 0, (hipStream_t)stream, h->prm, h->n, h->f64,
-                         h->i32, io, nullptr);
-    else if (envs == 32)
-      hipLaunchKernelGGL((step_kernel_wide<AR, 32>), gw, dim3(256), 0, (hipStream_t)stream, h->prm, h->n, h->f64,
-                         h->i32, io, nullptr);
-    else if (sp)
-      hipLaunchKernelGGL((step_kernel_wide<AR, 64, true>), gw, dim3(256), 0, (hipStream_t)stream, h->prm, h->n,
-                         h->f64, h->i32, io, sp);
-    else
-      hipLaunchKernelGGL((step_kernel_wide<AR, 64>), gw, dim3(256), 0, (hipStream_t)stream, h->prm, h->n, h->f64,
-                         h->i32, io, nullptr);
+    if (envs == 64) probed = step_kernel_wide<AR, 64, true>;
+  } else if (h->kind == 1) {
+    plain = step_kernel_split<AR>;
+  } else {
+    threads = 64;
   }
-  else if (h->split == 1)
-    hipLaunchKernelGGL(step_kernel_split<AR>, grid, dim3(256), 0, (hipStream_t)stream, h->prm, h->n, h->f64, h->i32,
-                       io);
-  else
-    hipLaunchKernelGGL(step_kernel<AR>, dim3(grid_for(h->n, 64)), dim3(64), 0, (hipStream_t)stream, h->prm, h->n,
-                       h->f64, h->i32, io);
+  const dim3 grid(grid_for(h->n, envs));
+  unsigned long long* sp = probed ? satrl_span::take(satrl_span::kEnvStep, (int64_t)grid.x * 4) : nullptr;
+  satrl_span::launch_span(probed, plain, sp, grid, dim3(threads), stream, h->prm, h->n, h->f64, h->i32, io);
 }
 
 }  // namespace
@@ -774,14 +756,14 @@ int satenv_default_params(satenv_params* p) {
 int satenv_set_step_kernel(satenv_env* h, int32_t kind, int32_t wide_envs) {
   if (!h || kind < 0 || kind > 2 || (wide_envs != 16 && wide_envs != 32 && wide_envs != 64))
     return fail(SATENV_ERR_ARG, "satenv_set_step_kernel: kind 0/1/2, wide_envs 16/32/64");
-  h->split = kind;
+  h->kind = kind;
   h->wide_envs = wide_envs;
   return SATENV_OK;
 }
 
 int satenv_create(satenv_env** out, int64_t num_envs, const satenv_params* p, int device) {
   if (!out || !p || num_envs <= 0) return fail(SATENV_ERR_ARG, "satenv_create: bad arguments");
-  if (!params_ok(p)) return fail(SATENV_ERR_ARG, "satenv_create: propagator must be 0/1/2, rk4_substeps >= 1");
+  if (!params_ok(*p)) return fail(SATENV_ERR_ARG, "satenv_create: propagator must be 0/1/2, rk4_substeps >= 1");
   HIP_TRY(hipSetDevice(device));
   satenv_env* h = new satenv_env();
   h->n = num_envs;
@@ -824,7 +806,7 @@ int satenv_num_envs(const satenv_env* h, int64_t* n) {
 
 int satenv_set_params(satenv_env* h, const satenv_params* p) {
   if (!h || !p) return fail(SATENV_ERR_ARG, "satenv_set_params: null");
-  if (!params_ok(p)) return fail(SATENV_ERR_ARG, "satenv_set_params: propagator must be 0/1/2, rk4_substeps >= 1");
+  if (!params_ok(*p)) return fail(SATENV_ERR_ARG, "satenv_set_params: propagator must be 0/1/2, rk4_substeps >= 1");
   h->prm = *p;
   return SATENV_OK;
 }

@@ -1,6 +1,7 @@
-// satenv_step.h -- one environment step (environment.py:81-255) per lane,
-// for both targets: the gfx950 kernels (satenv_kernels.hip) and the host
-// build of the same ABI (satenv_cpu.cpp, OpenMP over envs).
+// satenv_step.h -- one environment's init, reset and step (environment.py:
+// 26-255) per lane, for both targets: the gfx950 kernels (satenv_kernels.hip)
+// and the host build of the same ABI (satenv_cpu.cpp, OpenMP over envs).
+// step_lane is the whole step; the multi-wave kernels compose its pieces.
 //
 // Per-handle state layout (num_envs = N):
 //   f64 planes [16][N]  Pp0..2 Pv0..2 Ep0..2 Ev0..2 fuel_c fuel_t dis ep_return
@@ -17,6 +18,8 @@ constexpr int kPlaneDz = 0, kPlaneCount = 1, kPlaneBits = 2;
 
 struct alignas(8) F32x2 { float x, y; };
 
+inline bool params_ok(const Params& p) { return p.propagator >= 0 && p.propagator <= 2 && p.rk4_substeps >= 1; }
+
 struct StepIO {
   const float* pa;
   const float* ea;
@@ -29,6 +32,10 @@ struct StepIO {
   double* stats;
   int32_t* err;
 };
+
+// one env's share of a step's statistics (step_autoreset's stats_out): episode
+// finished, its return, the step's reward, capture
+struct StepStats { double fin = 0.0, fin_ret = 0.0, rew = 0.0, cap = 0.0; };
 
 SATENV_HD void write_obs(float* obs, double* obs64, int64_t i, const double (&k)[12]) {
   // [Pp-Ep, Pv-Ev, Pp, Pv, Ep, Ev]  environment.py:76-77,177-178
@@ -61,6 +68,38 @@ SATENV_HD void reset_kin(const Params& /*p*/, double (&k)[12]) {
   k[6] = 18000.0;
 }
 
+// env i as the constructor leaves it (environment.py:26-44)
+SATENV_HD void init_env(const Params& p, int64_t n, double* f64, int32_t* i32, int64_t i) {
+#pragma unroll
+  for (int c = 0; c < 12; ++c) f64[c * n + i] = p.init_kin[c];              // :30-33
+  f64[12 * n + i] = p.fuel_c0;                                              // :42-43
+  f64[13 * n + i] = p.fuel_t0;
+  f64[14 * n + i] = INFINITY;                                               // :44
+  f64[kPlaneRet * n + i] = 0.0;
+  i32[kPlaneDz * n + i] = 0;                                                // :41
+  i32[kPlaneCount * n + i] = 0;
+  i32[kPlaneBits * n + i] = make_bits(p.fuel_c0_mode, p.fuel_t0_mode, 1, p.flag);
+}
+
+// reset(Flag) of env i where the mask selects it (environment.py:66-79), and its obs either way
+SATENV_HD void reset_env(const Params& prm, int64_t n, double* f64, int32_t* i32, int32_t flag, const uint8_t* mask,
+                         float* obs, double* obs64, int64_t i) {
+  double k[12];
+  if (mask == nullptr || mask[i] != 0) {
+    reset_kin(prm, k);
+#pragma unroll
+    for (int c = 0; c < 12; ++c) f64[c * n + i] = k[c];
+    const int b = i32[kPlaneBits * n + i];
+    i32[kPlaneBits * n + i] = make_bits(fc_mode(b), ft_mode(b), 1, flag);
+    i32[kPlaneCount * n + i] = 0;
+    f64[kPlaneRet * n + i] = 0.0;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 12; ++c) k[c] = f64[c * n + i];
+  }
+  write_obs(obs, obs64, i, k);
+}
+
 // ---------------------------------------------------------------------------
 // One environment step (environment.py:81-255), one lane per env, in two
 // halves around the danger-zone count: step_begin (actions, fuel, STM,
@@ -77,7 +116,6 @@ struct Lane {
   bool terminal;          // reward/done final, no count: capture or timeout (:139-147 return first), or Flag 2
   double reward;
   bool done;
-  double cap;
 };
 
 // kRk45: the instantiation that carries propagator 2 (solve_ivp RK45); the
@@ -86,7 +124,7 @@ struct Lane {
 template <bool kRk45 = false>
 SATENV_HD void step_begin(const Params& prm, int64_t n, const double* __restrict__ f64,
                                            const int32_t* __restrict__ i32, const StepIO& io, int64_t i,
-                                           bool autoreset, Lane& L) {
+                                           bool autoreset, Lane& L, StepStats& s) {
   double* k = L.k;
 #pragma unroll
   for (int c = 0; c < 12; ++c) k[c] = f64[c * n + i];
@@ -169,12 +207,11 @@ SATENV_HD void step_begin(const Params& prm, int64_t n, const double* __restrict
     for (int c = 0; c < 12; ++c) k[c] = y[c];
   }
   L.dis = norm3(k[0] - k[6], k[1] - k[7], k[2] - k[8]);                   // :132
-  L.cap = 0.0;
   L.terminal = true;
   L.done = true;
   if (L.dis <= prm.d_capture) {                                           // :139-142, :221-225, :303-306
     L.reward = L.flag == 0 ? prm.win_reward : (L.flag == 1 ? -150.0 : 0.0);
-    L.cap = 1.0;
+    s.cap = 1.0;
   } else if (L.count >= prm.max_episode_steps) {                         // :144-147, :227-231, :308-311
     L.reward = L.flag == 0 ? prm.burn_reward : (L.flag == 1 ? prm.win_reward : 0.0);
   } else if (L.flag == 2) {                                               // :313-315: reward 0, not done,
@@ -225,16 +262,16 @@ SATENV_HD void step_reward(const Params& prm, Lane& L, int cnt) {
 
 SATENV_HD void step_end(const Params& prm, int64_t n, double* __restrict__ f64,
                                          int32_t* __restrict__ i32, const StepIO& io, int64_t i, bool autoreset,
-                                         Lane& L, double& fin, double& fin_ret, double& rew_acc) {
+                                         Lane& L, StepStats& s) {
   if (io.rew64) io.rew64[i] = L.reward;
   if (io.rew32) io.rew32[i] = (float)L.reward;
   if (io.done) io.done[i] = L.done ? 1 : 0;
   double ret = f64[kPlaneRet * n + i] + L.reward;
-  rew_acc = L.reward;
+  s.rew = L.reward;
   int vi_out = 0;
   if (autoreset && L.done) {                                              // CPPO_main.py:149-153 -> reset(Flag)
-    fin = 1.0;
-    fin_ret = ret;
+    s.fin = 1.0;
+    s.fin_ret = ret;
     ret = 0.0;
     reset_kin(prm, L.k);
     vi_out = 1;
@@ -252,10 +289,23 @@ SATENV_HD void step_end(const Params& prm, int64_t n, double* __restrict__ f64,
   i32[kPlaneBits * n + i] = make_bits(L.fcm, L.ftm, vi_out, L.flag);
 }
 
-SATENV_HD int lane_setup(const Params& prm, const Lane& L, DzCtx& z) {
-  const double* k = L.k;
-  return dz_setup(prm, k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8], k[9], k[10], k[11], L.fuel_c, L.fcm,
-                  z);
+// The whole step of env i in one lane (the count's four solves one after
+// another): the one-lane kernel and the host build.  Returns the error code
+// to record, 0 if none; the caller owns the (first-wins) error sink.
+template <bool kRk45>
+SATENV_HD int step_lane(const Params& prm, int64_t n, double* __restrict__ f64, int32_t* __restrict__ i32,
+                        const StepIO& io, int64_t i, bool autoreset, StepStats& s) {
+  Lane L;
+  step_begin<kRk45>(prm, n, f64, i32, io, i, autoreset, L, s);
+  int err = L.err;
+  if (!L.terminal) {
+    int cnt = 0;
+    const int rc = danger_zone(prm, L.k, L.fuel_c, L.fcm, cnt);            // :150, :317-332
+    if (err == 0) err = rc;
+    step_reward(prm, L, cnt);
+  }
+  step_end(prm, n, f64, i32, io, i, autoreset, L, s);
+  return err;
 }
 
 }  // namespace satenv

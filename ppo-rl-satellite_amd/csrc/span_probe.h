@@ -23,6 +23,16 @@ enum Kind { kRowpass = 0, kDw2 = 1, kReduce = 2, kAdam = 3, kPolicyAct = 4, kPol
 // with `waves` waves, or nullptr when no probe is set (or it is full)
 unsigned long long* take(int kind, int64_t waves);
 
+// One launch of a span-probed kernel: its measurement instantiation (SPAN =
+// true) when the probe handed this launch a span `sp`, else the plain one;
+// `sp` is the kernel's last argument either way.
+template <class... KA, class... A>
+void launch_span(void (*probed)(KA...), void (*plain)(KA...), unsigned long long* sp, dim3 grid, dim3 block,
+                 void* stream, A... args) {
+  void (*const k)(KA...) = sp ? probed : plain;
+  hipLaunchKernelGGL(k, grid, block, 0, (hipStream_t)stream, args..., sp);
+}
+
 __device__ __forceinline__ unsigned long long now() { return __builtin_amdgcn_s_memrealtime(); }
 
 // at a wave's exit: lane 0 stores (t0, now) for this wave (call it at every

@@ -426,3 +426,38 @@ def test_step_kernels_agree_bitwise(satrl_env):
     for k, out in runs.items():
         for a, b in zip(ref, out):
             assert torch.equal(a, b), k
+
+
+@pytest.mark.parametrize("flag", [0, 1])
+@pytest.mark.parametrize("n", [1, 63, 65, 130])
+def test_step_kernels_agree_bitwise_ragged(satrl_env, n, flag):
+    """The same agreement at the sizes where the kernels' shared lane head
+    and tail meet a ragged launch: one env, a partial wave (63), a partial
+    workgroup at each envs-per-workgroup setting (65, 130).  30 autoreset
+    steps with max_episode_steps=12, so every env is reset in-kernel twice,
+    and the steps between return non-zero danger-zone counts (seed 21 gives
+    both at every size, established on the host build)."""
+    E = satrl_env
+    T = 30
+    rng = np.random.default_rng(21)
+    pa = torch.tensor(rng.uniform(-1.6, 1.6, (T, n, 3)).astype(np.float32), device="cuda")
+    ea = torch.tensor(rng.uniform(-1.6, 1.6, (T, n, 3)).astype(np.float32), device="cuda")
+    runs = {}
+    for kind, wide in ((2, 64), (2, 32), (2, 16), (1, 64), (0, 64)):
+        env = E.VecSatellites(n, d_capture=15000.0, max_episode_steps=12)
+        env.set_step_kernel(kind, wide)
+        env.reset(flag)
+        out = []
+        for t in range(T):
+            obs, r, dn = env.step_autoreset(pa[t], ea[t])
+            out += [obs.clone(), r.clone(), dn.clone()] + [x.clone() for x in env.get_state()]
+        assert env.check_errors() == 0
+        runs[(kind, wide)] = out
+    ref = runs[(2, 64)]
+    done = torch.stack(ref[2::5])
+    dz = torch.stack([i32[0] for i32 in ref[4::5]])
+    assert bool(done.any())                                  # episodes ended: the autoreset path
+    assert bool(((done == 0) & (dz != 0)).any())             # a non-terminal step with a non-zero count
+    for k, out in runs.items():
+        for a, b in zip(ref, out):
+            assert torch.equal(a, b), k
