@@ -1691,10 +1691,30 @@ __global__ void __launch_bounds__(256) dw2_kernel(int mb, int S, int KR, int net
 // per instruction, six per wave) through a kKxD-slot ring with counted vmcnt
 // and raw s_barrier; the MFMA operands are ds_read_b128 of consecutive 16-B
 // (row groups 16 B apart in bank space).  Every sum has a fixed order.
+//
+// Each wave runs the chunk loop as a software pipeline: chunk c's 24 MFMAs
+// issue from one operand register set while chunk c+1's 12 ds_read_b128 fill
+// the other (in pairs, in first-use order) and the wave's six pieces of chunk
+// c+kKxAhead go out between them, one piece or one read pair per MFMA gap
+// over the chunk's first twelve MFMAs.  One s_barrier per chunk: behind it
+// every wave's pieces of chunk c+1 have landed and every wave's reads of the
+// slot about to be restaged are done.
 // ---------------------------------------------------------------------------
-constexpr int kKxD = 3;        // ring slots (chunks kKxD - 1 ahead; 4 and 5 measured no faster, round 6)
-// output tile width TW (64: 16 tiles per net, 8 splits of 512 rows at mb 4096;
-// 128: 4 tiles per net, half the plane bytes per workgroup, 32 splits)
+constexpr int kKxD = 3;        // ring slots (four: one workgroup per CU, the fused launch's reduce blocks wait: slower)
+// chunks the stream runs ahead of the MFMAs: kKxD (the slot restaged in
+// iteration c is chunk c's, already in registers; its reads are waited for in
+// front of the barrier) or kKxD - 1 (chunk c-1's; no LDS wait at the barrier)
+constexpr int kKxAhead = 3;
+static_assert(kKxAhead >= 2 && (kKxAhead == kKxD || kKxAhead == kKxD - 1), "see dw2_kx_body's barrier");
+// where a chunk's LDS reads (in pairs) and LDS-DMA pieces sit among its 24 MFMAs: pieces behind MFMAs 0, 2, .. 10,
+// read pairs behind 1, 3, .. 11 (dW2 span 8.7-9.1 us against 9.0-9.5 with the reads behind MFMAs 0-5 and the
+// pieces behind 6, 9, .. 21 in six alternations; pieces first and reads last, or all pieces back to back: no
+// faster; EXPERIMENTS.md)
+constexpr int kKxRd0 = 1, kKxRdS = 2, kKxPc0 = 0, kKxPcS = 2;
+// mfma6's (A plane, B plane) pairs in its order
+constexpr int kM6A[6] = {2, 0, 1, 1, 0, 0}, kM6B[6] = {0, 2, 1, 0, 1, 0};
+// output tile width (16 tiles per net, 8 splits of 512 rows at mb 4096); the
+// pipelined body's register sets and gap table are laid out for 64
 constexpr int kKxTW = 64;
 template <int TW>
 struct KxSmem {
@@ -1702,65 +1722,100 @@ struct KxSmem {
   unsigned char ring[kKxD][RUNS][KG];
 };
 // the body of dw2_kx_kernel for workgroup b: the slab tile of (net, tile, split)
-template <int TW>
 __device__ __forceinline__ void dw2_kx_body(int b, int mb, int S, int KR, int net_sel,
                                             const unsigned short* __restrict__ H1x,
                                             const unsigned short* __restrict__ dZ2x, float* __restrict__ p2,
-                                            KxSmem<TW>& sm) {
+                                            KxSmem<kKxTW>& sm) {
+  constexpr int TW = kKxTW;
+  static_assert(TW == 64, "one 1-KB piece per run, 2 x 2 tiles per wave");
   constexpr int H = 256, TT = H / TW, RUNS = KxSmem<TW>::RUNS;
-  constexpr int PPR = TW / 64;                                   // 1-KB pieces per run
-  constexpr int XN = TW / 32, PW = RUNS * PPR / 4;              // 16x16 tiles per wave side, pieces per wave
+  constexpr int XN = TW / 32, PW = RUNS / 4;                    // 16x16 tiles per wave side, pieces per wave
+  constexpr int NM = 6 * XN * XN, NR = 6 * XN;                  // MFMAs and ds_read_b128 per wave and chunk
+  // the gap table: read pair r behind MFMA kKxRd0 + r kKxRdS, piece k behind MFMA kKxPc0 + k kKxPcS
+  static_assert(kKxRd0 + (NR / 2 - 1) * kKxRdS < NM && kKxPc0 + (PW - 1) * kKxPcS < NM, "gaps of one chunk");
   auto& ring = sm.ring;
-  const int t = threadIdx.x, w = t >> 6, l = t & 63, li = l & 15, lg = l >> 4;
+  const int t = threadIdx.x, w = __builtin_amdgcn_readfirstlane(t >> 6), l = t & 63, li = l & 15, lg = l >> 4;
   const int s = b % S, tile = (b / S) % (TT * TT);
   const int net = net_sel < 0 ? b / (S * TT * TT) : net_sel;
   const int o0 = (tile / TT) * TW, n0 = (tile % TT) * TW;
   const int64_t PL = kx_rows(mb) * H;
   const int c_begin = s * (KR / 32), nch = (int)((min((int64_t)(s + 1) * KR, kx_rows(mb)) - (int64_t)s * KR) / 32);
-  // piece v = (run u, 64-column half h) of chunk c: 64 columns x 8 rows, 1 KB contiguous in the plane
-  auto stage = [&](int c) {
-    const int slot = c % kKxD, cg = 4 * (c_begin + c);             // first row group of the chunk
+  // piece k of wave w = run u = 4k + w (tensor k / 3, plane k % 3, row group w) of a chunk: 64 columns x 8
+  // rows, 1 KB contiguous in the plane; its chunk-0 source (a scalar base, the lane's 16 B) is loop-invariant
+  const unsigned short* src0[PW];
 #pragma unroll
-    for (int k = 0; k < PW; ++k) {
-      const int v = 4 * k + w, u = v / PPR, h = v % PPR;            // wave w: pieces w, w+4, ...
-      const int tz = u / 12, p = (u / 4) % 3, q = u % 4;
-      const unsigned short* src = (tz == 0 ? dZ2x : H1x) + (int64_t)net * 3 * PL + p * PL +
-                                  ((int64_t)(cg + q) * H + (tz == 0 ? o0 : n0) + 64 * h + l) * 8;
-      __builtin_amdgcn_global_load_lds(src, (lds_void_t*)&ring[slot][u][1024 * h], 16, 0, 0);
-    }
+  for (int k = 0; k < PW; ++k) {
+    const int u = 4 * k + w, tz = u / 12, p = (u / 4) % 3, q = u % 4;
+    src0[k] = (tz == 0 ? dZ2x : H1x) + (int64_t)net * 3 * PL + p * PL +
+              ((int64_t)(4 * c_begin + q) * H + (tz == 0 ? o0 : n0)) * 8;
+  }
+  auto piece = [&](int k, int c) {                                // this wave's piece k of chunk c
+    __builtin_amdgcn_global_load_lds(src0[k] + (int64_t)c * (4 * H * 8) + (unsigned)(l * 8),
+                                     (lds_void_t*)&ring[c % kKxD][4 * k + w][0], 16, 0, 0);
   };
   const int wo = w >> 1, wn = w & 1;
+  // A[o][k] = dZ2[row 8lg + k'][o], B[k][n] = H1[row][n]: group lg of plane p
+  const unsigned char* rdA = &ring[0][0 * 12 + lg][((TW / 2) * wo + li) * 16];
+  const unsigned char* rdB = &ring[0][1 * 12 + lg][((TW / 2) * wn + li) * 16];
+  // read j of a chunk, in the order the MFMAs first use them: plane pair j / (2 XN), then a[0], b[0], a[1], b[1]
+  auto rd = [&](int j, int slot, s8v (&a)[XN][3], s8v (&bq)[XN][3]) {
+    const int g = j / (2 * XN), x = (j % (2 * XN)) / 2;
+    const int off = slot * (int)sizeof(ring[0]) + x * 256;
+    if (j % 2 == 0) a[x][kM6A[g]] = *reinterpret_cast<const s8v*>(rdA + off + kM6A[g] * 4 * (int)sizeof(ring[0][0]));
+    else bq[x][kM6B[g]] = *reinterpret_cast<const s8v*>(rdB + off + kM6B[g] * 4 * (int)sizeof(ring[0][0]));
+  };
   f4 acc[XN][XN];
 #pragma unroll
   for (int x = 0; x < XN; ++x)
 #pragma unroll
     for (int y = 0; y < XN; ++y) acc[x][y] = f4{0.f, 0.f, 0.f, 0.f};
+  // one iteration: chunk c from (a, bq), chunk c+1 into (na, nb), chunk c+kKxAhead into the ring
+  auto iter = [&](int c, const s8v (&a)[XN][3], const s8v (&bq)[XN][3], s8v (&na)[XN][3], s8v (&nb)[XN][3]) {
+    // vmcnt: this wave's pieces of chunk c+1 landed (younger: chunks c+2 .. c+kKxAhead-1, PW each);
+    // lgkmcnt (kKxAhead == kKxD): its reads of chunk c, whose slot chunk c+kKxAhead takes, are done
+    if constexpr (kKxAhead == kKxD) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((kKxAhead - 2) * PW) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kKxAhead - 2) * PW) : "memory");
+    __builtin_amdgcn_s_barrier();   // every wave's: chunk c+1 readable, the slot of chunk c+kKxAhead free
+    const int cs = c + kKxAhead < nch ? c + kKxAhead : nch - 1;  // (tail: a harmless reload of the last chunk,
+    const int rslot = (c + 1 < nch ? c + 1 : nch - 1) % kKxD;    //  and a re-read of it that nothing uses)
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int c = 0; c < kKxD - 1; ++c) stage(c < nch ? c : nch - 1);
-  for (int c = 0; c < nch; ++c) {
-    // this wave's pieces of chunk c landed, and its reads of chunk c-1's slot are done
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((kKxD - 2) * PW) : "memory");
-    __builtin_amdgcn_s_barrier();                                                   // every wave's; slot c-1 free
-    stage(c + kKxD - 1 < nch ? c + kKxD - 1 : nch - 1);                             // (tail: a harmless reload)
-    const int slot = c % kKxD;
-    s8v a[XN][3], bq[XN][3];
-#pragma unroll
-    for (int x = 0; x < XN; ++x)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        // A[o][k] = dZ2[row 8lg + k'][o], B[k][n] = H1[row][n]: group lg of plane p
-        a[x][p] = *reinterpret_cast<const s8v*>(&ring[slot][0 * 12 + p * 4 + lg][((TW / 2) * wo + 16 * x + li) * 16]);
-        bq[x][p] = *reinterpret_cast<const s8v*>(&ring[slot][1 * 12 + p * 4 + lg][((TW / 2) * wn + 16 * x + li) * 16]);
+    for (int i = 0; i < NM; ++i) {
+      const int k = i / (XN * XN), x = (i / XN) % XN, y = i % XN;  // each accumulator: mfma6's six, in its order
+      acc[x][y] = mfma_bf16(a[x][kM6A[k]], bq[y][kM6B[k]], acc[x][y]);
+      __builtin_amdgcn_sched_barrier(0);
+      if (i >= kKxRd0 && (i - kKxRd0) % kKxRdS == 0 && (i - kKxRd0) / kKxRdS < NR / 2) {
+        rd(2 * ((i - kKxRd0) / kKxRdS), rslot, na, nb);
+        rd(2 * ((i - kKxRd0) / kKxRdS) + 1, rslot, na, nb);
       }
+      if (i >= kKxPc0 && (i - kKxPc0) % kKxPcS == 0 && (i - kKxPc0) / kKxPcS < PW) piece((i - kKxPc0) / kKxPcS, cs);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (c + kKxAhead >= nch) __builtin_amdgcn_s_setprio(0);       // (the last chunk is staged)
+  };
+  // acc[x][y][q] = dW2[o0 + (TW/2)wo + 16x + 4lg + q][n0 + (TW/2)wn + 16y + li]; the address is formed here so
+  // that no scalar load (of p2) is pending in the loop, where every LDS wait would wait for it too
+  float* out = p2 + ((int64_t)net * S + s) * H * H;
+  asm volatile("" : "+s"(out));
+  s8v ra[2][XN][3], rb[2][XN][3];
 #pragma unroll
-    for (int x = 0; x < XN; ++x)
+  for (int c = 0; c < kKxAhead; ++c)
 #pragma unroll
-      for (int y = 0; y < XN; ++y) acc[x][y] = mfma6(a[x], bq[y], acc[x][y]);
-    if (c + kKxD - 1 >= nch) __builtin_amdgcn_s_setprio(0);                         // (the last chunk is staged)
+    for (int k = 0; k < PW; ++k) piece(k, c < nch ? c : nch - 1);
+  // this wave's pieces of chunk 0 landed (younger: chunks 1 .. kKxAhead-1)
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kKxAhead - 1) * PW) : "memory");
+  __builtin_amdgcn_s_barrier();                                   // every wave's
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    rd(j, 0, ra[0], rb[0]);
+    __builtin_amdgcn_sched_barrier(0);                            // (in the loop's order)
+  }
+  for (int c = 0; c < nch; c += 2) {                              // (nch is the workgroup's: uniform branches)
+    iter(c, ra[0], rb[0], ra[1], rb[1]);
+    if (c + 1 >= nch) break;
+    iter(c + 1, ra[1], rb[1], ra[0], rb[0]);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  // acc[x][y][q] = dW2[o0 + (TW/2)wo + 16x + 4lg + q][n0 + (TW/2)wn + 16y + li]
-  float* out = p2 + ((int64_t)net * S + s) * H * H;
 #pragma unroll
   for (int x = 0; x < XN; ++x)
 #pragma unroll
@@ -1782,7 +1837,7 @@ __global__ void __launch_bounds__(256) dw2_kx_kernel(int mb, int S, int KR, int 
   // eight alternations on two boxes, equal (49.4) in three on a third;
   // bitwise the same (EXPERIMENTS.md round 5)
   __builtin_amdgcn_s_setprio(3);
-  dw2_kx_body<TW>(blockIdx.x, mb, S, KR, net_sel, H1x, dZ2x, p2, sm);
+  dw2_kx_body(blockIdx.x, mb, S, KR, net_sel, H1x, dZ2x, p2, sm);
   if constexpr (SPAN) satrl_span::exit(span, span_t0);
 }
 // split-K ways of dw2_kx_kernel: about kKxWgs workgroups, whole 32-row chunks,
@@ -2075,7 +2130,7 @@ __global__ void __launch_bounds__(256) dw2_kx_w1_kernel(int mb, int S, int KR, i
   __shared__ __attribute__((aligned(16))) KxSmem<TW> sm;
   if ((int)blockIdx.x < ndw) {
     __builtin_amdgcn_s_setprio(3);                               // (as dw2_kx_kernel)
-    dw2_kx_body<TW>(blockIdx.x, mb, S, KR, net_sel, H1x, dZ2x, p2, sm);
+    dw2_kx_body(blockIdx.x, mb, S, KR, net_sel, H1x, dZ2x, p2, sm);
   } else {
     // the reduce block's LDS (its float4 chunk sums, the block's norm pair)
     // inside the ring, which no block of this kind uses
