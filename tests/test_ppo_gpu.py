@@ -188,9 +188,11 @@ def test_update_matches_reference_h64_configs1(case):
 
 @pytest.mark.parametrize("H,split,mb", [(64, False, 512), (256, False, 512), (256, True, 512),
                                          (256, False, 777), (64, False, 100),
-                                         (256, False, 4096), (64, False, 4096)])
+                                         (256, False, 4096), (64, False, 4096),
+                                         (128, False, 512), (128, False, 100)])
 def test_fused_step_vs_torch_autograd(H, split, mb):
-    """The product's minibatch step (H 64: rowpass_dw2 + reduce + Adam; H 256:
+    """The product's minibatch step (H 64: rowpass_dw2 + reduce + Adam; H 128:
+    rowpass + dw2 + reduce + Adam; H 256:
     rowpass_kx + dw2_kx + reduce + Adam, 16-row blocks at mb <= 1024) vs plain
     torch fp32 autograd + clip_grad_norm_ + torch.optim.Adam on the same
     minibatch; mb 777 / 100 are ragged (the last BatchSampler minibatch with
@@ -467,7 +469,7 @@ def test_update_graph_groups_equal_eager():
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("H,N", [(256, 1000), (256, 65536), (64, 4096), (64, 65536)])
+@pytest.mark.parametrize("H,N", [(256, 1000), (256, 65536), (64, 4096), (64, 65536), (128, 1000)])
 def test_policy_act_and_value_kernels(H, N):
     """satrl_policy_act / satrl_policy_value vs the torch modules + satrl_gaussian_sample
     (same Philox draw); every row independent of N and of its position (bitwise).
