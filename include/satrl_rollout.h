@@ -11,6 +11,10 @@
  *                              rollout is identical for any env sharding
  *   satrl_moments           <- adv.mean() / adv.std() of ppo_continuous.py:210
  *                              (f64 sum and sum of squares, for a global all-reduce)
+ *   satrl_obs_normalize     <- normalization.py:38-47 Normalization.__call__ with
+ *                              frozen statistics, plus per-slot f64 moment sums
+ *   satrl_return_scan       <- normalization.py:50-63 RewardScaling's running return
+ *                              and its per-slot f64 moment sums
  *
  * All pointers are device buffers, calls are async on `stream` (hipStream_t,
  * NULL = default) and graph-capturable.  Return 0 or a negative error code.
@@ -39,6 +43,31 @@ int satrl_gaussian_sample(int64_t N, const float* mean, const float* log_std, fl
 
 /* out f64[2] += (sum x, sum x^2) over x f32 [n]  (out must be zeroed first) */
 int satrl_moments(int64_t n, const float* x, double* out, void* stream);
+
+/* Running observation normalisation (normalization.py:38-47, frozen statistics).
+ * raw, out f32 [N][18], two different buffers; stats f32 [2][18] (mean row,
+ * inv_std row) and pivot f32 [18] are device buffers read on every launch, so
+ * a captured hipGraph replays with whatever the caller last wrote there.
+ * out = clamp((raw - mean) * inv_std, +-clip): one f32 subtract, one f32
+ * multiply, no FMA; clip <= 0 = no clamp.  If acc is non-NULL (then pivot
+ * must be too) it is f64 [ceil(N/32)][2][18]: for slot k (rows 32k .. 32k+31)
+ * and every feature acc[k][0] += sum d, acc[k][1] += sum d*d with
+ * d = (double)raw - (double)pivot, rows past N contributing nothing.  The
+ * order of a slot's terms depends on the row's index in the slot only and
+ * there are no atomics (a plain read-modify-write by the slot's owner; calls
+ * are ordered by the stream), so acc is bitwise reproducible and a shard
+ * starting at a multiple of 32 envs writes the unsharded run's slots.       */
+int satrl_obs_normalize(int64_t N, const float* raw, const float* stats, float clip, float* out, const float* pivot,
+                        double* acc, void* stream);
+
+/* Discounted-return scan of RewardScaling (normalization.py:50-63): r f32
+ * [T][N] and done u8 [T][N] time-major as satrl_gae reads them, one lane per
+ * env, forward over t: R = gamma * R + (double)r[t][i] in f64 (no FMA), the
+ * slot's sum of R and of R*R added to acc f64 [ceil(N/32)][2] (fixed in-slot
+ * order, no atomics), then R = 0 where done[t][i].  carry f64 [N] is R on
+ * entry (t = 0) and is written after t = T-1.                               */
+int satrl_return_scan(int64_t T, int64_t N, const float* r, const uint8_t* done, double gamma, double* carry,
+                      double* acc, void* stream);
 
 const char* satrl_last_error(void);
 

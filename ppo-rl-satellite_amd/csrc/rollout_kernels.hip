@@ -86,9 +86,192 @@ __global__ void __launch_bounds__(256) moments_kernel(int64_t n, const float* __
   }
 }
 
+// ---------------------------------------------------------------------------
+// Running observation normalisation (normalization.py:38-47 with frozen
+// statistics): out = clamp((raw - mean) * inv_std, +-clip), one subtract and
+// one multiply in f32.  One wave per 32-env slot: the slot's 576 floats are
+// 144 16-byte lane loads (three per lane, the third on lanes 0..15).
+//
+// Accumulators (acc != NULL): the slot's raw rows are staged in LDS; lane
+// f + 18 h (f < 18, h < 2) sums d = (double)raw - (double)pivot[f] and d*d
+// over rows 16 h .. 16 h + 15 in row order, the two halves are added (low +
+// high) and the slot's owner lane adds the total to acc[slot] with a plain
+// read-modify-write.  The order depends on the row's index in the slot only,
+// so the sums are bitwise reproducible and a shard that starts at a multiple
+// of 32 envs writes the unsharded run's slots.
+// ---------------------------------------------------------------------------
+constexpr int kObsDim = 18;
+constexpr int kSlotRows = 32;
+constexpr int kSlotFloats = kSlotRows * kObsDim;   // 576
+constexpr int kSlotVec4 = kSlotFloats / 4;         // 144
+
+__device__ __forceinline__ float clamp_keep_nan(float x, float c) { return x < -c ? -c : (x > c ? c : x); }
+
+__global__ void __launch_bounds__(64) obs_normalize_kernel(int64_t N, const float* __restrict__ raw,
+                                                           const float* __restrict__ stats, float clip,
+                                                           float* __restrict__ out, const float* __restrict__ pivot,
+                                                           double* __restrict__ acc, int vec) {
+  __shared__ float s_stats[2 * kObsDim];
+  __shared__ float s_pivot[kObsDim];
+  __shared__ __attribute__((aligned(16))) float s_raw[kSlotFloats];
+  const int lane = threadIdx.x;
+  const int64_t slot = blockIdx.x;
+  const int64_t base = slot * kSlotFloats;          // first float of the slot
+  const int64_t lim = N * kObsDim;                  // one past the last float of raw / out
+  // every global load of the launch is issued before the first wait: the statistics, the
+  // lane's pieces of the slot and the owner lanes' accumulator words
+  const float sv = lane < 2 * kObsDim ? stats[lane] : 0.0f;
+  const float pv = acc && lane < kObsDim ? pivot[lane] : 0.0f;
+  double* const a = acc ? acc + slot * (2 * kObsDim) : nullptr;
+  double a0 = 0.0, a1 = 0.0;
+  if (acc && lane < kObsDim) { a0 = a[lane]; a1 = a[kObsDim + lane]; }
+  float x[3][4];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int j = lane + 64 * k;                    // the lane's k-th 16-byte piece of the slot
+    const int64_t e = base + 4 * j;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) x[k][c] = 0.0f;
+    if (j >= kSlotVec4 || e >= lim) continue;
+    if (vec && e + 4 <= lim) {
+      const float4 v = *reinterpret_cast<const float4*>(raw + e);
+      x[k][0] = v.x; x[k][1] = v.y; x[k][2] = v.z; x[k][3] = v.w;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (e + c < lim) x[k][c] = raw[e + c];
+    }
+  }
+  if (lane < 2 * kObsDim) s_stats[lane] = sv;
+  if (lane < kObsDim) s_pivot[lane] = pv;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int j = lane + 64 * k;
+    if (acc && j < kSlotVec4) *reinterpret_cast<float4*>(s_raw + 4 * j) = make_float4(x[k][0], x[k][1], x[k][2], x[k][3]);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int j = lane + 64 * k;
+    const int64_t e = base + 4 * j;
+    if (j >= kSlotVec4 || e >= lim) continue;
+    float y[4];
+    int f = (4 * j) % kObsDim;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float z = (x[k][c] - s_stats[f]) * s_stats[kObsDim + f];
+      y[c] = clip > 0.0f ? clamp_keep_nan(z, clip) : z;
+      f = f + 1 == kObsDim ? 0 : f + 1;
+    }
+    if (vec && e + 4 <= lim) {
+      *reinterpret_cast<float4*>(out + e) = make_float4(y[0], y[1], y[2], y[3]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (e + c < lim) out[e + c] = y[c];
+    }
+  }
+  if (!acc) return;                                  // (uniform: a kernel argument)
+  const int64_t left = N - slot * kSlotRows;
+  const int rows = left < kSlotRows ? (int)left : kSlotRows;
+  const int f = lane % kObsDim, h = lane / kObsDim;  // lanes 36.. idle (h >= 2): they re-read half 0
+  const int r0 = h < 2 ? 16 * h : 0;
+  const double p = (double)s_pivot[f];
+  float v[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) v[q] = s_raw[(r0 + q) * kObsDim + f];   // the 16 LDS reads in flight together
+  double s = 0.0, s2 = 0.0;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {                     // row order; a row past N adds +0.0, which is exact
+    const double d = r0 + q < rows ? (double)v[q] - p : 0.0;
+    s += d;
+    s2 += d * d;
+  }
+  const double hs = __shfl_down(s, kObsDim, 64);     // lane f takes rows 16..31 from lane f + 18
+  const double hs2 = __shfl_down(s2, kObsDim, 64);
+  if (lane < kObsDim) {
+    a[lane] = a0 + (s + hs);
+    a[kObsDim + lane] = a1 + (s2 + hs2);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Discounted-return scan of RewardScaling (normalization.py:50-63): one lane
+// per env, forward over t, R = gamma * R + r in f64 (no FMA); the lane sums R
+// and R * R over t in registers, R = 0 after a done step.  A slot's 32 lanes
+// are then combined by an xor butterfly (16, 8, 4, 2, 1; a + b == b + a, so
+// the pairing depends on the lane's index in the slot only) and lane 0 of the
+// slot adds the totals to acc[slot] with a plain read-modify-write.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) return_scan_kernel(int64_t T, int64_t N, const float* __restrict__ r,
+                                                         const uint8_t* __restrict__ done, double gamma,
+                                                         double* __restrict__ carry, double* __restrict__ acc) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  const bool live = i < N;
+  const int64_t ii = live ? i : N - 1;               // idle lanes re-read the last env and contribute nothing
+  double R = carry[ii];
+  double s = 0.0, s2 = 0.0;
+#pragma unroll 8
+  for (int64_t t = 0; t < T; ++t) {
+    const int64_t o = t * N + ii;
+    R = gamma * R + (double)r[o];
+    s += R;
+    s2 += R * R;
+    if (done[o]) R = 0.0;
+  }
+  if (live) carry[i] = R;
+  else { s = 0.0; s2 = 0.0; }
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) {
+    s += __shfl_xor(s, off, 64);
+    s2 += __shfl_xor(s2, off, 64);
+  }
+  if (live && (threadIdx.x & 31) == 0) {
+    double* a = acc + (i >> 5) * 2;
+    a[0] += s;
+    a[1] += s2;
+  }
+}
+
+int fail(const char* what) {
+  g_err = what;
+  return -1;
+}
+
 }  // namespace
 
 extern "C" {
+
+int satrl_obs_normalize(int64_t N, const float* raw, const float* stats, float clip, float* out, const float* pivot,
+                        double* acc, void* stream) {
+  if (N <= 0) return fail("satrl_obs_normalize: N must be positive");
+  if (!raw) return fail("satrl_obs_normalize: raw is NULL");
+  if (!stats) return fail("satrl_obs_normalize: stats is NULL");
+  if (!out) return fail("satrl_obs_normalize: out is NULL");
+  if (raw == out) return fail("satrl_obs_normalize: out must not be raw");
+  if (acc && !pivot) return fail("satrl_obs_normalize: pivot is NULL with a non-NULL acc");
+  const int64_t slots = (N + kSlotRows - 1) / kSlotRows;
+  // 16-byte lane accesses need both row buffers on a 16-byte boundary (a slot is 2304 bytes)
+  const int vec = (((uintptr_t)raw | (uintptr_t)out) & 15) == 0;
+  hipLaunchKernelGGL(obs_normalize_kernel, dim3((unsigned)slots), dim3(64), 0, (hipStream_t)stream, N, raw, stats,
+                     clip, out, pivot, acc, vec);
+  HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+int satrl_return_scan(int64_t T, int64_t N, const float* r, const uint8_t* done, double gamma, double* carry,
+                      double* acc, void* stream) {
+  if (T <= 0) return fail("satrl_return_scan: T must be positive");
+  if (N <= 0) return fail("satrl_return_scan: N must be positive");
+  if (!r) return fail("satrl_return_scan: r is NULL");
+  if (!done) return fail("satrl_return_scan: done is NULL");
+  if (!carry) return fail("satrl_return_scan: carry is NULL");
+  if (!acc) return fail("satrl_return_scan: acc is NULL");
+  hipLaunchKernelGGL(return_scan_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, T, N, r,
+                     done, gamma, carry, acc);
+  HIP_CHECK_LAUNCH();
+  return 0;
+}
 
 int satrl_gae(int64_t T, int64_t N, const float* r, const uint8_t* done, const float* v, float gamma, float lamda,
               float* adv_out, float* vtarget_out, void* stream) {

@@ -11,7 +11,8 @@
   advantage normalisation, and the graph-captured minibatch update.
   One process per GPU; with a process group the envs are sharded by global
   env id (Philox noise keyed by it, so rollouts do not depend on sharding)
-  and gradients are averaged with RCCL.
+  and gradients are averaged with RCCL.  Opt-in (obs_norm, reward_scaling):
+  running observation normalisation and reward scaling, satrl/norm.py.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ import numpy as np
 import torch
 
 from . import dist as _dist
+from . import norm as _norm
 from .buffer import ReplayBuffer, RolloutBuffer
 from .env import VecSatellites
 from .ppo import PPO_continuous, PPOLearner, gae, gaussian_sample, policy_act, policy_value
@@ -36,7 +38,8 @@ class args_param:  # noqa: N801
                  use_lr_decay=True, use_grad_clip=True, use_orthogonal_init=True, set_adam_eps=True, use_tanh=True,
                  chkpt_dir="/mnt/datab/home/yuanwenzheng/PICTURE1",
                  num_envs=1, horizon=None, seed=0, rollout_graph_chunk=64, update_graph_group=64, device=None,
-                 surrogate=False, dp_minibatch="global", minibatch_sampler=None, allreduce="rccl"):
+                 surrogate=False, dp_minibatch="global", minibatch_sampler=None, allreduce="rccl",
+                 obs_norm=False, reward_scaling=False, obs_clip=10.0, obs_norm_calib_steps=64):
         self.max_train_steps = max_train_steps
         self.evaluate_freq = evaluate_freq
         self.save_freq = save_freq
@@ -94,6 +97,18 @@ class args_param:  # noqa: N801
         # (satrl_ppo_allreduce_peer: a two-shot reduce-scatter + all-gather
         # over IPC-mapped buffers, fused with reduce_dp; satrl/peer.py)
         self.allreduce = allreduce
+        # running observation normalisation and reward scaling of the vectorised
+        # engine (normalization.py's Normalization / RewardScaling, satrl/norm.py).
+        # The reference's own use_state_norm / use_reward_norm / use_reward_scaling
+        # above stay what they are there: printed and never read.  obs_norm: the
+        # policy and the update see clamp((obs - mean) / (std + 1e-8), +-obs_clip)
+        # under statistics frozen per iteration, first estimated over
+        # obs_norm_calib_steps throw-away steps (0: start from the identity);
+        # reward_scaling: GAE reads rew / (std of the running discounted return + 1e-8)
+        self.obs_norm = obs_norm
+        self.reward_scaling = reward_scaling
+        self.obs_clip = obs_clip
+        self.obs_norm_calib_steps = obs_norm_calib_steps
         # set by the train_* functions from the env (CPPO_main.py:99-101)
         self.state_dim = 18
         self.action_dim = 3
@@ -268,6 +283,13 @@ class VecTrainer:
         self.T = int(args.horizon)
         self.env_offset = int(env_offset)
         self.seed = int(args.seed)
+        self.obs_norm = bool(getattr(args, "obs_norm", False))
+        self.reward_scaling = bool(getattr(args, "reward_scaling", False))
+        if (self.obs_norm or self.reward_scaling) and pg is not None and (self.N % _norm.SLOT or
+                                                                          self.env_offset % _norm.SLOT):
+            # every rank holds whole accumulator slots (satrl/norm.py slot_total)
+            raise ValueError(f"obs_norm / reward_scaling under data parallelism need num_envs % {_norm.SLOT} == 0 "
+                             f"(got num_envs={self.N}, env_offset={self.env_offset})")
         args.state_dim, args.action_dim, args.max_action = 18, 3, 1.6
         self.env = VecSatellites(self.N, device=self.device, d_capture=d_capture,
                                  max_episode_steps=args.max_episode_steps, Flag=self.flag)
@@ -300,7 +322,116 @@ class VecTrainer:
             sd = args.surrogate if isinstance(args.surrogate, (str, dict)) else "trained"
             self.surrogate = Surrogate(device=self.device, seed=self.seed, state_dict=sd)
             self.ellipse_params = torch.zeros((self.N, 10), dtype=torch.float32, device=self.device)
-        self.env.reset(self.flag, obs_out=self.buf.obs[0])
+        if self.obs_norm or self.reward_scaling:
+            self._setup_norm(args)
+        self._reset_obs()
+        if self.obs_norm and int(getattr(args, "obs_norm_calib_steps", 64)) > 0:
+            self._calibrate_obs_norm(int(args.obs_norm_calib_steps))
+
+    # -- running normalisation (satrl/norm.py) ------------------------------------------
+    def _setup_norm(self, args):
+        """State of obs_norm / reward_scaling.  The accumulators are per 32-env
+        slot (global env id // 32), so that their total does not depend on the
+        sharding: under data parallelism every rank holds whole slots."""
+        f64 = dict(dtype=torch.float64, device=self.device)
+        slots = _norm.num_slots(self.N)
+        self._first_slot = self.env_offset // _norm.SLOT if self.pg is not None else 0
+        self._global_slots = slots * _dist.world_size(self.pg)
+        if self.obs_norm:
+            self.obs_clip = float(getattr(args, "obs_clip", 10.0))
+            self.obs_rms = _norm.RunningMoments((18,))
+            self.obs_raw = torch.zeros((self.N, 18), dtype=torch.float32, device=self.device)
+            self.obs_stats = torch.zeros((2, 18), dtype=torch.float32, device=self.device)
+            self.obs_pivot = torch.zeros(18, dtype=torch.float32, device=self.device)
+            self.obs_acc = torch.zeros((slots, 2, 18), **f64)
+            self._obs_acc_rows = 0                           # local rows summed into obs_acc
+            self._write_obs_stats()
+        if self.reward_scaling:
+            self.ret_rms = _norm.RunningMoments(())
+            self.ret_carry = torch.zeros(self.N, **f64)
+            self.ret_acc = torch.zeros((slots, 2), **f64)
+            self.rew_s = torch.zeros((self.T, self.N), dtype=torch.float32, device=self.device)
+
+    def _write_obs_stats(self):
+        """obs_rms -> the device statistics, in place (the captured rollout
+        graphs read them on every replay); the pivot of the next sums is the
+        mean in f32."""
+        st = self.obs_rms.device_stats()
+        self.obs_stats.copy_(torch.from_numpy(st))
+        self.obs_pivot.copy_(torch.from_numpy(st[0].copy()))
+
+    def _reset_obs(self):
+        """Every env restarts; buf.obs[0] is the (normalised) reset observation."""
+        if not self.obs_norm:
+            self.env.reset(self.flag, obs_out=self.buf.obs[0])
+            return
+        self.env.reset(self.flag, obs_out=self.obs_raw)
+        _norm.obs_normalize(self.obs_raw, self.obs_stats, self.obs_clip, self.buf.obs[0])
+
+    def _fold_obs_stats(self):
+        """The iteration's slot sums -> obs_rms -> the device statistics; obs_acc is zeroed."""
+        tot = _norm.slot_total(self.obs_acc, self.pg, self._first_slot, self._global_slots)
+        self.obs_rms.merge_shifted(self._obs_acc_rows * _dist.world_size(self.pg), tot[0], tot[1],
+                                   self.obs_pivot.cpu().numpy())
+        self._write_obs_stats()
+        self.obs_acc.zero_()
+        self._obs_acc_rows = 0
+
+    def _calibrate_obs_norm(self, steps):
+        """First statistics from `steps` eager throw-away steps under the
+        identity (mean 0, inv_std 1) with the reset observation's row 0 as the
+        pivot; the env state, env.stats and the step counters are restored."""
+        piv = self.obs_raw[0].clone()
+        _dist.broadcast_([piv], self.pg)
+        self.obs_pivot.copy_(piv)
+        f, i = self.env.get_state()
+        st, raw0 = self.env.stats.clone(), self.obs_raw.clone()
+        for s_ in range(steps):
+            self.step_base.fill_(s_)
+            self._policy_step(0)
+            self.buf.obs[0].copy_(self.buf.obs[1])
+        self._obs_acc_rows += steps * self.N
+        self.env.set_state(f, i)
+        self.env.stats.copy_(st)
+        self.obs_raw.copy_(raw0)
+        self.step_base.zero_()
+        if self.ellipse_params is not None:
+            self.ellipse_params.zero_()
+        self._fold_obs_stats()
+        _norm.obs_normalize(self.obs_raw, self.obs_stats, self.obs_clip, self.buf.obs[0])
+
+    def normalize_obs(self, raw, out=None):
+        """Raw observations f32 [n, 18] as the policy sees them under the
+        current statistics (the identity without obs_norm)."""
+        if not self.obs_norm:
+            return raw if out is None else out.copy_(raw)
+        out = torch.empty_like(raw) if out is None else out
+        return _norm.obs_normalize(raw, self.obs_stats, self.obs_clip, out)
+
+    def norm_state(self):
+        """The running statistics as numpy arrays: a policy trained with
+        obs_norm is meaningless without them."""
+        return {"obs": self.obs_rms.state_dict() if self.obs_norm else None,
+                "ret": self.ret_rms.state_dict() if self.reward_scaling else None,
+                "carry": self.ret_carry.cpu().numpy() if self.reward_scaling else None}
+
+    def load_norm_state(self, d):
+        """Restore norm_state() and rewrite the device tensors; buf.obs[0] is
+        normalised again from the current raw observation."""
+        if self.obs_norm:
+            if d.get("obs") is None:
+                raise ValueError("no observation statistics in this state (obs_norm is on)")
+            self.obs_rms.load_state_dict(d["obs"])
+            self._write_obs_stats()
+            _norm.obs_normalize(self.obs_raw, self.obs_stats, self.obs_clip, self.buf.obs[0])
+        if self.reward_scaling:
+            if d.get("ret") is None or d.get("carry") is None:
+                raise ValueError("no return statistics in this state (reward_scaling is on)")
+            self.ret_rms.load_state_dict(d["ret"])
+            carry = torch.from_numpy(np.ascontiguousarray(d["carry"], dtype=np.float64))
+            if tuple(carry.shape) != (self.N,):
+                raise ValueError(f"carry of shape {tuple(carry.shape)} for {self.N} envs")
+            self.ret_carry.copy_(carry)
 
     STRATA = 8
 
@@ -370,7 +501,12 @@ class VecTrainer:
         if events is not None:
             events[0].record()
         if env:
-            self.env.step_autoreset(pa, ea, obs_out=buf.obs[t + 1], reward_out=buf.rew[t], done_out=buf.done[t])
+            if self.obs_norm:                    # raw row -> the fixed scratch, normalised into the buffer
+                self.env.step_autoreset(pa, ea, obs_out=self.obs_raw, reward_out=buf.rew[t], done_out=buf.done[t])
+                _norm.obs_normalize(self.obs_raw, self.obs_stats, self.obs_clip, buf.obs[t + 1], self.obs_pivot,
+                                    self.obs_acc)
+            else:
+                self.env.step_autoreset(pa, ea, obs_out=buf.obs[t + 1], reward_out=buf.rew[t], done_out=buf.done[t])
         if events is not None:
             events[1].record()
         if self.surrogate is not None:            # env.ellipse_params of the state the policy sees next
@@ -386,7 +522,7 @@ class VecTrainer:
             raise ValueError("Flag 0 (pursuer) or 1 (evader)")
         self.flag = flag
         self.learner = self.pursuer if flag == 0 else self.evader
-        self.env.reset(flag, obs_out=self.buf.obs[0])
+        self._reset_obs()
 
     def self_play(self, phases, iterations_per_phase, timers=None):
         """Alternating training (the reference's Sign == 0 runs
@@ -430,6 +566,8 @@ class VecTrainer:
                 self._policy_step(0)
                 self.env.set_state(f, i)
                 self.env.stats.copy_(st)
+                if self.obs_norm:                # the warm-up row is not part of the iteration's sums
+                    self.obs_acc.zero_()
                 torch.cuda.synchronize()
             for c in range(nchunks):
                 self._chunk_graph(c).replay()
@@ -437,22 +575,43 @@ class VecTrainer:
             for t in range(self.T):
                 self._policy_step(t)
         self.rollout_steps += self.T
+        if self.obs_norm:
+            self._obs_acc_rows += self.T * self.N
 
     # -- learning -----------------------------------------------------------------
     def compute_advantages(self, chunk_steps=64):
         buf, L = self.buf, self.learner
         with torch.no_grad():
             policy_value(L.H, buf.obs.view(-1, 18), L.P, buf.values.view(-1))     # critic(s), all T+1 rows
-            gae(buf.rew, buf.done, buf.values, L.gamma, L.lamda, adv_out=buf.adv, vt_out=buf.vtarget)
+            gae(self._scaled_rewards() if self.reward_scaling else buf.rew, buf.done, buf.values, L.gamma, L.lamda,
+                adv_out=buf.adv, vt_out=buf.vtarget)
             adv_n = L.normalize_adv(buf.adv.reshape(-1))
             buf.pack(adv_n)
+
+    def _scaled_rewards(self):
+        """RewardScaling (normalization.py:50-63) over the iteration: the
+        running discounted return of every env is scanned forward (R = 0 after
+        a done step), its moments are merged into ret_rms, and GAE reads
+        rew / (std + 1e-8).  buf.rew and the env's episode statistics stay raw."""
+        buf = self.buf
+        _norm.return_scan(buf.rew, buf.done, self.learner.gamma, self.ret_carry, self.ret_acc)
+        tot = _norm.slot_total(self.ret_acc, self.pg, self._first_slot, self._global_slots)
+        self.ret_acc.zero_()
+        self.ret_rms.merge_shifted(self.T * self.N * _dist.world_size(self.pg), tot[0], tot[1], 0.0)
+        scale = np.float32(1.0 / (float(self.ret_rms.std()) + _norm.EPS))
+        torch.mul(buf.rew, float(scale), out=self.rew_s)
+        return self.rew_s
 
     def update(self):
         self.learner.update_packed(self.buf.packed, self.episodes, perms=lambda ep: self.epoch_perm())
 
     def finish_iteration(self):
         # next rollout starts from the current observation
-        self.buf.obs[0].copy_(self.buf.obs[self.T])
+        if self.obs_norm:                        # ... seen under the statistics the next iteration freezes
+            self._fold_obs_stats()
+            _norm.obs_normalize(self.obs_raw, self.obs_stats, self.obs_clip, self.buf.obs[0])
+        else:
+            self.buf.obs[0].copy_(self.buf.obs[self.T])
         st = _dist.sum_(self.env.stats, self.pg)
         self.episodes = float(st[0].item())
         self.iteration_count += 1
