@@ -196,6 +196,17 @@ int satrl_ppo_rowpass_fault_inject(int group, unsigned value, void* stream);
 int satrl_policy_act(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
                      uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act0,
                      float* logp0, float* act1, float* logp1, void* stream);
+/* satrl_policy_eval <- PPO_continuous.evaluate (ppo_continuous.py:168-174) on
+ * satrl_policy_act's forward path, block shape and agent interleave; actions
+ * only, no log-probs.  Agent a (0: P0, 1: P1) with bit 1 << a of det_mask
+ * set acts with the mean, a = max_action*tanh(mean_layer); an agent whose bit
+ * is clear samples, and its action is bit for bit the one satrl_policy_act
+ * writes for the same (seed, agent, env_offset + row, step + *step_base).
+ * -1 before any device call: H not 64/128/256, N <= 0, a NULL obs, P0 or
+ * act0, det_mask outside 0..3, bit 1 set without P1, P1 without act1.     */
+int satrl_policy_eval(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
+                      int det_mask, uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base,
+                      float* act0, float* act1, void* stream);
 /* critic value v f32 [N] of the flat parameters P (net 1) <- self.critic(s),
  * ppo_continuous.py:200-201                                               */
 int satrl_policy_value(int H, int64_t N, const float* obs, const float* P, float* v_out, void* stream);

@@ -15,6 +15,10 @@
  *                              frozen statistics, plus per-slot f64 moment sums
  *   satrl_return_scan       <- normalization.py:50-63 RewardScaling's running return
  *                              and its per-slot f64 moment sums
+ *   satrl_episode_record    <- CPPO_main.py:233-282 test_network's bookkeeping
+ *                              (epsiode_reward += r until done), per env: the
+ *                              first episode's return, length, outcome, closest
+ *                              and final distance and commanded delta-v
  *
  * All pointers are device buffers, calls are async on `stream` (hipStream_t,
  * NULL = default) and graph-capturable.  Return 0 or a negative error code.
@@ -68,6 +72,27 @@ int satrl_obs_normalize(int64_t N, const float* raw, const float* stats, float c
  * entry (t = 0) and is written after t = T-1.                               */
 int satrl_return_scan(int64_t T, int64_t N, const float* r, const uint8_t* done, double gamma, double* carry,
                       double* acc, void* stream);
+
+/* Episode records of a policy evaluation: every env's FIRST episode after the
+ * reset call, one lane per env, SoA planes.
+ *   rec_f64 f64 [5][N]: ret (sum of rewards), final_dis, min_dis, dv_p, dv_e
+ *                       (sums of (|a0| + |a1|) + |a2| of pa / ea, in f64)
+ *   rec_i32 i32 [2][N]: length, outcome (0 running, 1 captured, 2 timed out)
+ *   alive   i32 [1]:    the envs whose outcome is still 0
+ * reset: ret = dv_p = dv_e = 0, min_dis = +inf, final_dis = NaN, length =
+ * outcome = 0, *alive = N.  record (after a satenv_step without autoreset:
+ * reward f64 [N] and done u8 [N] are its outputs, obs64 f64 [N][18] its
+ * observation, pa / ea f32 [N][3] the actions it was given) touches only envs
+ * with outcome 0: adds the reward and the two action sums in f64 in call
+ * order, counts the step, takes dis = sqrt((o0*o0 + o1*o1) + o2*o2) of
+ * obs64[i][0:3] into min_dis, and where done[i] stores final_dis = dis and
+ * outcome = (reward == capture_reward) ? 1 : 2 -- the env writes its terminal
+ * rewards as exact literals -- and takes the env off *alive (one vector atomic
+ * per wave).  N <= 0 or a NULL pointer: -1 before any device call.         */
+int satrl_episode_record_reset(int64_t N, double* rec_f64, int32_t* rec_i32, int32_t* alive, void* stream);
+int satrl_episode_record(int64_t N, const double* reward, const uint8_t* done, const double* obs64, const float* pa,
+                         const float* ea, double capture_reward, double* rec_f64, int32_t* rec_i32, int32_t* alive,
+                         void* stream);
 
 const char* satrl_last_error(void);
 

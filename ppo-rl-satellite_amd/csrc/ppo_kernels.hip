@@ -1520,6 +1520,10 @@ __global__ void __launch_bounds__(kCsWaves * 64) rowpass_cs_kernel(
 //           parameter sets (blockIdx % nagents = agent: P0 pursuer, P1
 //           evader; the actor is net 0 of each flat layout)
 //   MODE 1  critic value (net 1 of P0), ppo_continuous.py:200-201
+//   MODE 2  evaluation: MODE 0's forward and agent interleave, actions only.
+//           Agent a with bit 1 << a of det_mask set acts with the mean,
+//           max_action*tanh(.) (PPO_continuous.evaluate, ppo_continuous.py:
+//           168-174); the other one with MODE 0's clamped sample, bit for bit
 // ---------------------------------------------------------------------------
 // rows per policy/value workgroup (64-row tiles measured 62 vs 58.5 us per
 // rollout step at 16k envs: fewer, larger workgroups lose more to the tail
@@ -1536,7 +1540,8 @@ __global__ void __launch_bounds__(NW * 64) policy_kernel(int64_t N, const float*
                                                      const uint64_t* __restrict__ step_base,
                                                      float* __restrict__ act0, float* __restrict__ logp0,
                                                      float* __restrict__ act1, float* __restrict__ logp1,
-                                                     float* __restrict__ value, unsigned long long* __restrict__ span) {
+                                                     float* __restrict__ value, int det_mask,
+                                                     unsigned long long* __restrict__ span) {
   const unsigned long long span_t0 = SPAN ? satrl_span::now() : 0ull;
   constexpr int R = kPolRows, RT = R / 16, CT = H / 16 / NW;
   // Two or more workgroups share a CU, and one finishing its output layer
@@ -1547,8 +1552,8 @@ __global__ void __launch_bounds__(NW * 64) policy_kernel(int64_t N, const float*
   __builtin_amdgcn_s_setprio(3);
   const Layout L = layout(H);
   __shared__ MlpSmem<H, NW, R> sm;
-  const int agent = MODE == 0 ? (int)(blockIdx.x % nagents) : 0;
-  const int64_t r0 = (int64_t)(MODE == 0 ? blockIdx.x / nagents : blockIdx.x) * R;
+  const int agent = MODE != 1 ? (int)(blockIdx.x % nagents) : 0;
+  const int64_t r0 = (int64_t)(MODE != 1 ? blockIdx.x / nagents : blockIdx.x) * R;
   const float* P = agent == 0 ? P0 : P1;
   const int nvalid = (int)(N - r0 < R ? N - r0 : R);
   auto gather = [&](int t0, int nt) {
@@ -1577,7 +1582,7 @@ __global__ void __launch_bounds__(NW * 64) policy_kernel(int64_t N, const float*
   float h1[RT][CT][4];
   float w3[CT][3];
   unsigned h1w[RT][CT][6];
-  mlp_forward<H, NW, R, false, true>(sm, P, MODE == 0 ? 0 : 1, nvalid, gather, nullptr, acc, h1, w3, h1w);
+  mlp_forward<H, NW, R, false, true>(sm, P, MODE != 1 ? 0 : 1, nvalid, gather, nullptr, acc, h1, w3, h1w);
   const int r = threadIdx.x;
   if (r >= nvalid) {                                             // no barrier follows
     if constexpr (SPAN) satrl_span::exit(span, span_t0);
@@ -1589,10 +1594,29 @@ __global__ void __launch_bounds__(NW * 64) policy_kernel(int64_t N, const float*
     if constexpr (SPAN) satrl_span::exit(span, span_t0);
     return;
   }
+  float* act = agent == 0 ? act0 : act1;
+  if constexpr (MODE == 2) {
+    if ((det_mask >> agent) & 1) {                               // (uniform: the workgroup's agent)
+#pragma unroll
+      for (int d = 0; d < 3; ++d)
+        act[i * 3 + d] = max_action * tanh_f32(out_sum<H / 16>(sm.osum, r, d) + P[L.b3a + d]);   // evaluate()
+      if constexpr (SPAN) satrl_span::exit(span, span_t0);
+      return;
+    }
+  }
   float z[4];
   philox_normal4((uint64_t)(env_offset + i), step + (step_base ? *step_base : 0ull), agent == 0 ? k00 : k10,
                  agent == 0 ? k01 : k11, z);
-  float* act = agent == 0 ? act0 : act1;
+  if constexpr (MODE == 2) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const float mu = max_action * tanh_f32(out_sum<H / 16>(sm.osum, r, d) + P[L.b3a + d]);
+      float lp;                                                  // (dead: MODE 0's expression for the action alone)
+      gaussian_act(mu, P[L.ls + d], z[d], max_action, act[i * 3 + d], lp);
+    }
+    if constexpr (SPAN) satrl_span::exit(span, span_t0);
+    return;
+  }
   float* logp = agent == 0 ? logp0 : logp1;
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
@@ -3044,7 +3068,24 @@ int satrl_policy_act(int H, int64_t N, const float* obs, const float* P0, const 
   philox_key(seed, 1, k10, k11);
   launch_policy<0>(H, satrl_span::kPolicyAct, dim3((unsigned)(nag * ((N + kPolRows - 1) / kPolRows))), stream, N, obs,
                    P0, P1, nag, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, logp0, act1, logp1,
-                   nullptr);
+                   nullptr, 0);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int satrl_policy_eval(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
+                      int det_mask, uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base,
+                      float* act0, float* act1, void* stream) {
+  if (!valid_h(H) || N <= 0 || !obs || !P0 || !act0) return -1;
+  if (det_mask < 0 || det_mask > 3 || ((det_mask & 2) && !P1)) return -1;
+  if (P1 && !act1) return -1;
+  const int nag = P1 ? 2 : 1;
+  uint32_t k00, k01, k10, k11;
+  philox_key(seed, 0, k00, k01);
+  philox_key(seed, 1, k10, k11);
+  launch_policy<2>(H, satrl_span::kPolicyAct, dim3((unsigned)(nag * ((N + kPolRows - 1) / kPolRows))), stream, N, obs,
+                   P0, P1, nag, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, nullptr, act1,
+                   nullptr, nullptr, det_mask);
   LAUNCH_CHECK();
   return 0;
 }
@@ -3053,7 +3094,7 @@ int satrl_policy_value(int H, int64_t N, const float* obs, const float* P, float
   if (!valid_h(H) || N <= 0 || !obs || !P || !v_out) return -1;
   launch_policy<1>(H, satrl_span::kPolicyValue, dim3((unsigned)((N + kPolRows - 1) / kPolRows)), stream, N, obs, P,
                    nullptr, 1, 0.0f, 0u, 0u, 0u, 0u, (int64_t)0, (uint64_t)0, nullptr, nullptr, nullptr, nullptr,
-                   nullptr, v_out);
+                   nullptr, v_out, 0);
   LAUNCH_CHECK();
   return 0;
 }

@@ -233,6 +233,63 @@ __global__ void __launch_bounds__(64) return_scan_kernel(int64_t T, int64_t N, c
   }
 }
 
+// ---------------------------------------------------------------------------
+// Episode records of an evaluation (one lane per env, SoA planes): the first
+// episode of every env is summed in f64 in step order and frozen at its done
+// step.  rec_f64 planes: ret, final_dis, min_dis, dv_p, dv_e; rec_i32 planes:
+// length, outcome (0 running, 1 captured, 2 timed out).  *alive counts the
+// envs still running: a wave's newly finished envs are counted by a ballot
+// and taken off by one vector atomic of its first lane.
+// ---------------------------------------------------------------------------
+constexpr int kRecRet = 0, kRecFinalDis = 1, kRecMinDis = 2, kRecDvP = 3, kRecDvE = 4;
+constexpr int kRecLength = 0, kRecOutcome = 1;
+
+__global__ void __launch_bounds__(64) episode_record_reset_kernel(int64_t N, double* __restrict__ rf,
+                                                                  int32_t* __restrict__ ri,
+                                                                  int32_t* __restrict__ alive) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i == 0) *alive = (int32_t)N;
+  if (i >= N) return;
+  rf[kRecRet * N + i] = 0.0;
+  rf[kRecFinalDis * N + i] = __builtin_nan("");
+  rf[kRecMinDis * N + i] = __builtin_inf();
+  rf[kRecDvP * N + i] = 0.0;
+  rf[kRecDvE * N + i] = 0.0;
+  ri[kRecLength * N + i] = 0;
+  ri[kRecOutcome * N + i] = 0;
+}
+
+__device__ __forceinline__ double abs_sum3(const float* __restrict__ a) {
+  return (fabs((double)a[0]) + fabs((double)a[1])) + fabs((double)a[2]);
+}
+
+__global__ void __launch_bounds__(64) episode_record_kernel(int64_t N, const double* __restrict__ reward,
+                                                            const uint8_t* __restrict__ done,
+                                                            const double* __restrict__ obs64,
+                                                            const float* __restrict__ pa, const float* __restrict__ ea,
+                                                            double capture_reward, double* __restrict__ rf,
+                                                            int32_t* __restrict__ ri, int32_t* __restrict__ alive) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  bool finished = false;
+  if (i < N && ri[kRecOutcome * N + i] == 0) {
+    const double r = reward[i];
+    const double* o = obs64 + i * kObsDim;
+    const double dis = sqrt((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]);
+    rf[kRecRet * N + i] += r;
+    rf[kRecDvP * N + i] += abs_sum3(pa + i * 3);
+    rf[kRecDvE * N + i] += abs_sum3(ea + i * 3);
+    ri[kRecLength * N + i] += 1;
+    if (dis < rf[kRecMinDis * N + i]) rf[kRecMinDis * N + i] = dis;
+    if (done[i]) {
+      rf[kRecFinalDis * N + i] = dis;
+      ri[kRecOutcome * N + i] = r == capture_reward ? 1 : 2;
+      finished = true;
+    }
+  }
+  const unsigned long long m = __ballot(finished);               // (every lane of the wave is here)
+  if (m != 0ull && threadIdx.x == 0) atomicSub(alive, (int32_t)__popcll(m));
+}
+
 int fail(const char* what) {
   g_err = what;
   return -1;
@@ -269,6 +326,28 @@ int satrl_return_scan(int64_t T, int64_t N, const float* r, const uint8_t* done,
   if (!acc) return fail("satrl_return_scan: acc is NULL");
   hipLaunchKernelGGL(return_scan_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, T, N, r,
                      done, gamma, carry, acc);
+  HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+int satrl_episode_record_reset(int64_t N, double* rec_f64, int32_t* rec_i32, int32_t* alive, void* stream) {
+  if (N <= 0) return fail("satrl_episode_record_reset: N must be positive");
+  if (N > INT32_MAX) return fail("satrl_episode_record_reset: *alive is an int32");
+  if (!rec_f64 || !rec_i32 || !alive) return fail("satrl_episode_record_reset: a NULL buffer");
+  hipLaunchKernelGGL(episode_record_reset_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
+                     N, rec_f64, rec_i32, alive);
+  HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+int satrl_episode_record(int64_t N, const double* reward, const uint8_t* done, const double* obs64, const float* pa,
+                         const float* ea, double capture_reward, double* rec_f64, int32_t* rec_i32, int32_t* alive,
+                         void* stream) {
+  if (N <= 0) return fail("satrl_episode_record: N must be positive");
+  if (!reward || !done || !obs64 || !pa || !ea || !rec_f64 || !rec_i32 || !alive)
+    return fail("satrl_episode_record: a NULL buffer");
+  hipLaunchKernelGGL(episode_record_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, N,
+                     reward, done, obs64, pa, ea, capture_reward, rec_f64, rec_i32, alive);
   HIP_CHECK_LAUNCH();
   return 0;
 }

@@ -105,6 +105,8 @@ _SIGS = {
     "satrl_moments": ([_i64, _vp, _vp, _vp], C.c_int),
     "satrl_obs_normalize": ([_i64, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp], C.c_int),
     "satrl_return_scan": ([_i64, _i64, _vp, _vp, C.c_double, _vp, _vp, _vp], C.c_int),
+    "satrl_episode_record_reset": ([_i64, _vp, _vp, _vp, _vp], C.c_int),
+    "satrl_episode_record": ([_i64, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp], C.c_int),
     "satrl_last_error": ([], C.c_char_p),
     "satrl_ppo_layout": ([C.c_int, C.POINTER(_i64)], C.c_int),
     "satrl_ppo_sizes": ([C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)], C.c_int),
@@ -145,6 +147,8 @@ _SIGS = {
                                   _vp], C.c_int),
     "satrl_policy_act": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_uint64, _i64, C.c_uint64, _vp, _vp, _vp, _vp,
                           _vp, _vp], C.c_int),
+    "satrl_policy_eval": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_int, C.c_uint64, _i64, C.c_uint64, _vp, _vp,
+                           _vp, _vp], C.c_int),
     "satrl_policy_value": ([C.c_int, _i64, _vp, _vp, _vp, _vp], C.c_int),
     "satrl_ppo_stage": ([_i64, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "satrl_ppo_group_advance": ([_vp, _vp], C.c_int),

@@ -150,6 +150,51 @@ def policy_act(H, obs, P0, P1, max_action, seed, env_offset, step, act0, logp0, 
                                       ptr(logp0), ptr(act1), ptr(logp1), stream_ptr()), "satrl_policy_act")
 
 
+def policy_eval(H, obs, P0, P1, max_action, det_mask, seed, env_offset, step, act0, act1=None, step_base=None):
+    """Both agents' actions without log-probs (satrl_policy_eval): agent a
+    with bit 1 << a of det_mask set acts with the mean (PPO_continuous.evaluate),
+    the other one with policy_act's sample for the same noise key."""
+    N = obs.shape[0]
+    _lib.require_cuda(obs, torch.float32, (N, 18), "obs")
+    for t, nm in ((act0, "act0"),) + (((act1, "act1"),) if P1 is not None else ()):
+        _lib.require_cuda(t, torch.float32, (N, 3), nm)
+    check(_lib.lib().satrl_policy_eval(int(H), N, ptr(obs), ptr(P0), ptr(P1), float(max_action), int(det_mask),
+                                       int(seed) & (2**64 - 1), int(env_offset), int(step), ptr(step_base), ptr(act0),
+                                       ptr(act1), stream_ptr()), "satrl_policy_eval")
+
+
+REC_F64 = ["ret", "final_dis", "min_dis", "dv_p", "dv_e"]
+REC_I32 = ["length", "outcome"]
+
+
+def episode_record_reset(rec_f64, rec_i32, alive):
+    """Episode records as before any step (satrl_episode_record_reset)."""
+    N = rec_f64.shape[1]
+    _lib.require_cuda(rec_f64, torch.float64, (len(REC_F64), N), "rec_f64")
+    _lib.require_cuda(rec_i32, torch.int32, (len(REC_I32), N), "rec_i32")
+    _lib.require_cuda(alive, torch.int32, (1,), "alive")
+    check(_lib.lib().satrl_episode_record_reset(N, ptr(rec_f64), ptr(rec_i32), ptr(alive), stream_ptr()),
+          "satrl_episode_record_reset")
+
+
+def episode_record(reward, done, obs64, pa, ea, capture_reward, rec_f64, rec_i32, alive):
+    """One env step into the records of every env's first episode
+    (satrl_episode_record): reward f64 [N], done u8 [N], obs64 f64 [N,18] of
+    VecSatellites.step, pa / ea f32 [N,3] the actions it was given."""
+    N = reward.shape[0]
+    _lib.require_cuda(reward, torch.float64, (N,), "reward")
+    _lib.require_cuda(done, torch.uint8, (N,), "done")
+    _lib.require_cuda(obs64, torch.float64, (N, 18), "obs64")
+    _lib.require_cuda(pa, torch.float32, (N, 3), "pa")
+    _lib.require_cuda(ea, torch.float32, (N, 3), "ea")
+    _lib.require_cuda(rec_f64, torch.float64, (len(REC_F64), N), "rec_f64")
+    _lib.require_cuda(rec_i32, torch.int32, (len(REC_I32), N), "rec_i32")
+    _lib.require_cuda(alive, torch.int32, (1,), "alive")
+    check(_lib.lib().satrl_episode_record(N, ptr(reward), ptr(done), ptr(obs64), ptr(pa), ptr(ea),
+                                          float(capture_reward), ptr(rec_f64), ptr(rec_i32), ptr(alive),
+                                          stream_ptr()), "satrl_episode_record")
+
+
 def policy_value(H, obs, P, v_out):
     """critic(obs) on the fused MLP kernel (satrl_policy_value)."""
     N = obs.shape[0]

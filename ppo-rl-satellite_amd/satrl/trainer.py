@@ -13,6 +13,8 @@
   env id (Philox noise keyed by it, so rollouts do not depend on sharding)
   and gradients are averaged with RCCL.  Opt-in (obs_norm, reward_scaling):
   running observation normalisation and reward scaling, satrl/norm.py.
+  ``VecTrainer.evaluate`` measures the current policies on a fresh env handle
+  without touching any training state, satrl/evaluate.py.
 """
 from __future__ import annotations
 
@@ -315,6 +317,8 @@ class VecTrainer:
         self.iteration_count = 0
         self.rollout_steps = 0
         self.episodes = 0.0
+        self.evaluations = []                                # train(evaluate_every=...): (iteration, episodes, summary)
+        self._evaluators = {}                                # evaluate(): one cached VecEvaluator per num_envs
         self.surrogate = None
         self.ellipse_params = None
         if getattr(args, "surrogate", False):
@@ -624,13 +628,43 @@ class VecTrainer:
         `for epsiode in range(max_train_steps)`), and lr_decay is at 0."""
         return self.episodes >= self.args.max_train_steps
 
-    def train(self, max_iterations=None, timers=None):
+    def train(self, max_iterations=None, timers=None, evaluate_every=None, **eval_kwargs):
         """Iterations until the episode budget (or max_iterations) is reached;
-        returns the per-iteration statistics."""
+        returns the per-iteration statistics.  evaluate_every=k: after every
+        k-th iteration, evaluate(**eval_kwargs) and append (iteration_count,
+        episodes, summary) to self.evaluations (args.evaluate_freq, which
+        counts the reference's N = 1 steps, stays unread)."""
         out = []
         while not self.budget_reached and (max_iterations is None or len(out) < max_iterations):
             out.append(self.iteration(timers))
+            if evaluate_every and len(out) % int(evaluate_every) == 0:
+                self.evaluations.append((self.iteration_count, self.episodes,
+                                         self.evaluate(**eval_kwargs).summary()))
         return out
+
+    # -- evaluation (satrl/evaluate.py) -----------------------------------------------------
+    def evaluate(self, num_envs=None, deterministic="learner", max_steps=None, states=None, seed=None, record=False):
+        """The current policies on a fresh env handle of the evaluator's own
+        (`num_envs` envs, default N, this env's parameters): every env's first
+        episode, at most max_steps steps (default max_episode_steps), as an
+        EvalResult (per-env records and summary()).
+
+        deterministic: which agents act with their mean ("learner", the
+        default: the agent this Flag trains; "both"; "none"; or a set of
+        "pursuer" / "evader"); the others sample as in the rollout, keyed by
+        `seed` (default args.seed ^ evaluate.EVAL_SEED_XOR), agent id, global
+        env id and a step counter that starts at 0, so equal calls give equal
+        bits.  states=(f64_planes, i32_planes): start from these env states
+        (VecSatellites.set_state) instead of reset(Flag).  record=True keeps
+        the per-step streams (EvalResult.streams).  No state of the trainer
+        changes.  Under data parallelism each rank evaluates its own envs;
+        results are not reduced across ranks."""
+        from .evaluate import VecEvaluator
+        n = self.N if num_envs is None else int(num_envs)
+        if n not in self._evaluators:
+            self._evaluators[n] = VecEvaluator(self, n)
+        return self._evaluators[n].evaluate(deterministic=deterministic, max_steps=max_steps, states=states, seed=seed,
+                                            record=record)
 
     def iteration(self, timers=None):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
