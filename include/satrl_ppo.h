@@ -211,6 +211,41 @@ int satrl_policy_eval(int H, int64_t N, const float* obs, const float* P0, const
  * ppo_continuous.py:200-201                                               */
 int satrl_policy_value(int H, int64_t N, const float* obs, const float* P, float* v_out, void* stream);
 
+/* Update diagnostics: what an update did to the policy and the critic, from
+ * the forward pass of both nets over n rows src[idx[r]] of the packed table
+ * (idx nullable: rows 0..n-1, as satrl_ppo_rowpass).  Forward only, on the
+ * rowpass's own gather and MLP code in the policy kernel's shape (a workgroup
+ * per 32-row block and net), so every ratio is the bits the loss head would
+ * form and every v the bits of satrl_policy_value; nothing of the update is
+ * read but P and nothing written.  The pad columns of src are never read.
+ * Per row, in f32 exactly as the loss head: d = logp(a|s) - logp_old, ratio =
+ * expf(d), s1 = ratio*adv, s2 = clamp(ratio, 1 -+ epsilon)*adv, v = critic(s);
+ * then in f64 from those f32 values the slots of sums f64 [SATRL_DIAG_N]:
+ *   ROWS      n
+ *   SURR      sum min(s1, s2)          (policy loss = -SURR / n)
+ *   KL        sum (ratio - 1) - d      (the k3 estimator of KL(old || new))
+ *   LOGRATIO  sum d
+ *   CLIPPED   rows with ratio < 1 - epsilon or ratio > 1 + epsilon
+ *   RATIO_MAX max ratio
+ *   VERR2     sum (v - vt)^2           (value loss = VERR2 / n)
+ *   VERR      sum (vt - v)
+ *   VT, VT2   sum vt, sum vt^2
+ * No atomics: each block adds its 32 rows in row order into a line of
+ * scratch (f64, at least satrl_ppo_diagnostics_scratch(n) elements), and one
+ * or (above 4096 blocks) two small launches add the lines in a fixed order,
+ * so sums is bitwise reproducible for equal (n, src, idx, P).
+ * rows_out (nullable) f32 [n][4] = ratio, d, v, 0 in the call's row order:
+ * the parity hook, as satrl_ppo_rowpass_ratio's ratio.
+ * Asynchronous on `stream`, no host synchronisation.  -1 before any device
+ * call (and satrl_ppo_last_error set): H not 64/128/256, n <= 0 or above
+ * 2^31 - 65, a NULL src, P, sums or scratch, scratch_len too small.        */
+enum { SATRL_DIAG_ROWS = 0, SATRL_DIAG_SURR, SATRL_DIAG_KL, SATRL_DIAG_LOGRATIO, SATRL_DIAG_CLIPPED,
+       SATRL_DIAG_RATIO_MAX, SATRL_DIAG_VERR2, SATRL_DIAG_VERR, SATRL_DIAG_VT, SATRL_DIAG_VT2, SATRL_DIAG_N };
+int64_t satrl_ppo_diagnostics_scratch(int64_t n);
+int satrl_ppo_diagnostics(int H, int64_t n, const float* src, const int64_t* idx, const float* P, float epsilon,
+                          float max_action, double* sums, double* scratch, int64_t scratch_len, float* rows_out,
+                          void* stream);
+
 /* Minibatch staging for a graph-replayed group of minibatches
  * (BatchSampler(SubsetRandomSampler) order, ppo_continuous.py:217): rows
  * [0, rows) of stage f32 [rows][32] = src[perm[group[0] * rows + r]] (packed

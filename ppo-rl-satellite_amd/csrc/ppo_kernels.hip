@@ -1627,6 +1627,143 @@ __global__ void __launch_bounds__(NW * 64) policy_kernel(int64_t N, const float*
 }
 
 // ---------------------------------------------------------------------------
+// Update diagnostics (satrl_ppo_diagnostics): the forward pass of both nets
+// over rows src[idx[r]] of the packed table and, per (32-row block, net)
+// workgroup, f64 partial sums of what the loss head sees -- the policy
+// kernel's shape (kPolRows rows, its wave counts and its wave priority) on the
+// rowpass's gather, head constants and mlp_forward, so ratio and v are the
+// update's own bits.  No gradient, nothing of the update is written.
+// A block's partial is one 128-B line of `part` f64 [row block][16]:
+//   actor  [0..7]  rows, sum min(s1, s2), sum kl, sum d, clipped rows, max ratio, 0, 0
+//   critic [8..15] sum (v - vt)^2, sum (vt - v), sum vt, sum vt^2, 0, 0, 0, 0
+// Lanes 0..31 of wave 0 hold a row each; lane q < 8 then adds the block's 32
+// values of slot q in row order (rows past n contribute 0), so a partial
+// depends on the block's rows alone.  diag_reduce_kernel adds the lines.
+// ---------------------------------------------------------------------------
+constexpr int kDiagLine = 16;       // f64 per row block of `part`
+constexpr int kDiagChunk = 4096;    // lines per workgroup of the first reduce level
+
+template <int H, int NW>
+__global__ void __launch_bounds__(NW * 64) diag_kernel(int n, const float* __restrict__ src,
+                                                       const int64_t* __restrict__ idx, const float* __restrict__ P,
+                                                       float epsilon, float max_action, double* __restrict__ part,
+                                                       float* __restrict__ rows_out) {
+  constexpr int R = kPolRows, RT = R / 16, CT = H / 16 / NW, NT = NW * 64;
+  __builtin_amdgcn_s_setprio(3);                                  // (as policy_kernel: until phase B's loads are out)
+  __shared__ MlpSmem<H, NW, R> sm;
+  __shared__ float ax[R][8];
+  __shared__ float hcs[3][3];
+  __shared__ float hb3s[4];
+  __shared__ double red[5][R + 1];                                 // (+1: the adding lanes on distinct banks)
+  const int net = (int)blockIdx.x & 1, rb = (int)blockIdx.x >> 1, r0 = rb * R;
+  float hls_d, hb3_d;
+  head_load<H, NT>(P, hls_d, hb3_d);
+  f4 acc[RT][CT];
+  float h1[RT][CT][4];
+  float w3[CT][3];
+  unsigned h1w[RT][CT][6];
+  auto gather = [&](int t0, int nt) {
+    gather_rows<R, NT>(n, src, idx, r0, t0, nt, sm.S, ax, hls_d, hb3_d, hcs, hb3s);
+  };
+  mlp_forward<H, NW, R, false, true>(sm, P, net, n - r0, gather, nullptr, acc, h1, w3, h1w);
+  const int r = threadIdx.x, row = r0 + r;
+  if (r < R) {
+    double q[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (row < n) {
+      if (net == 0) {
+        // (the loss head's f32 expressions, in its order)
+        float logp[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          const float th = tanh_f32(out_sum<H / 16>(sm.osum, r, d) + hb3s[d]);
+          const float mu = max_action * th;
+          const float var = hcs[0][d];
+          const float dv = ax[r][d] - mu;
+          logp[d] = (-(dv * dv) / (2.0f * var) - hcs[1][d]) - kLogSqrt2Pi;
+        }
+        const float lsum = (logp[0] + logp[1]) + logp[2];
+        const float lold = (ax[r][3] + ax[r][4]) + ax[r][5];
+        const float dl = lsum - lold;
+        const float ratio = expf(dl);
+        const float adv = ax[r][6];
+        const float s1 = ratio * adv;
+        const float cr = fminf(fmaxf(ratio, 1.0f - epsilon), 1.0f + epsilon);
+        const float s2 = cr * adv;
+        const bool clipped = ratio < 1.0f - epsilon || ratio > 1.0f + epsilon;
+        q[0] = fmin((double)s1, (double)s2);
+        q[1] = ((double)ratio - 1.0) - (double)dl;
+        q[2] = (double)dl;
+        q[3] = clipped ? 1.0 : 0.0;
+        q[4] = (double)ratio;
+        if (rows_out != nullptr) {
+          rows_out[(int64_t)row * 4 + 0] = ratio;
+          rows_out[(int64_t)row * 4 + 1] = dl;
+        }
+      } else {
+        const float vc = out_sum<H / 16>(sm.osum, r, 0) + hb3s[3];
+        const double vt = (double)ax[r][7], e = (double)vc - vt;
+        q[0] = e * e;
+        q[1] = -e;
+        q[2] = vt;
+        q[3] = vt * vt;
+        if (rows_out != nullptr) {
+          rows_out[(int64_t)row * 4 + 2] = vc;
+          rows_out[(int64_t)row * 4 + 3] = 0.0f;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) red[k][r] = q[k];
+  }
+  __syncthreads();
+  if (r < 8) {
+    // actor: slot 0 the row count, 1..4 sums of red[0..3], 5 the max of red[4];
+    // critic: slots 0..3 sums of red[0..3]
+    const int k = net == 0 ? r - 1 : r;
+    double s = 0.0;
+    if (k >= 0 && k < 4) {
+      for (int i = 0; i < R; ++i) s += red[k][i];
+    } else if (net == 0 && r == 5) {
+      for (int i = 0; i < R; ++i) s = fmax(s, red[4][i]);
+    } else if (net == 0 && r == 0) {
+      s = (double)(n - r0 < R ? n - r0 : R);
+    }
+    part[(int64_t)rb * kDiagLine + 8 * net + r] = s;
+  }
+}
+
+// out line b = the lines in[b * chunk .. (b + 1) * chunk) added in a fixed
+// order (slot 5: their max): thread (j, slot) of the 64 x 16 takes lines j,
+// j + 64, ... of the chunk in turn, then slot threads of j = 0 add the 64
+// partials in j order.  `final`: the one workgroup writes the SATRL_DIAG_N
+// slots of `sums` instead of a line.
+__global__ void __launch_bounds__(1024) diag_reduce_kernel(const double* __restrict__ in, int64_t nin, int chunk,
+                                                           double* __restrict__ out, int final) {
+  __shared__ double sh[64][kDiagLine + 1];
+  const int t = threadIdx.x, slot = t & 15, j = t >> 4;
+  const int64_t b0 = (int64_t)blockIdx.x * chunk;
+  const int64_t b1 = b0 + chunk < nin ? b0 + chunk : nin;
+  double s = 0.0;
+  if (slot == 5) {
+    for (int64_t b = b0 + j; b < b1; b += 64) s = fmax(s, in[b * kDiagLine + slot]);
+  } else {
+    for (int64_t b = b0 + j; b < b1; b += 64) s += in[b * kDiagLine + slot];
+  }
+  sh[j][slot] = s;
+  __syncthreads();
+  if (j != 0) return;
+  s = sh[0][slot];
+  for (int k = 1; k < 64; ++k) s = slot == 5 ? fmax(s, sh[k][slot]) : s + sh[k][slot];
+  if (!final) {
+    out[(int64_t)blockIdx.x * kDiagLine + slot] = s;
+  } else if (slot < 6) {
+    out[slot] = s;                                                 // rows .. ratio max
+  } else if (slot >= 8 && slot < 12) {
+    out[slot - 2] = s;                                             // value error^2 .. vt^2
+  }
+}
+
+// ---------------------------------------------------------------------------
 // dW2 = dZ2^T H1 per net (fc2.weight.grad), split-K over the minibatch rows.
 // Workgroup (net, 64x64 output tile, split s) sums rows [s*KR, (s+1)*KR) of
 // its tile into slab p2[net][s] with f32 MFMA 16x16x4 (4 waves; wave w owns
@@ -3095,6 +3232,50 @@ int satrl_policy_value(int H, int64_t N, const float* obs, const float* P, float
   launch_policy<1>(H, satrl_span::kPolicyValue, dim3((unsigned)((N + kPolRows - 1) / kPolRows)), stream, N, obs, P,
                    nullptr, 1, 0.0f, 0u, 0u, 0u, 0u, (int64_t)0, (uint64_t)0, nullptr, nullptr, nullptr, nullptr,
                    nullptr, v_out, 0);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// f64 elements of satrl_ppo_diagnostics' scratch: a line per 32-row block, and
+// above kDiagChunk blocks a line per chunk of them (the first reduce level)
+int64_t satrl_ppo_diagnostics_scratch(int64_t n) {
+  if (n <= 0 || n > (int64_t)0x7FFFFFFF - 2 * kPolRows) return -1;
+  const int64_t nrb = (n + kPolRows - 1) / kPolRows;
+  return kDiagLine * (nrb + (nrb > kDiagChunk ? (nrb + kDiagChunk - 1) / kDiagChunk : 0));
+}
+
+int satrl_ppo_diagnostics(int H, int64_t n, const float* src, const int64_t* idx, const float* P, float epsilon,
+                          float max_action, double* sums, double* scratch, int64_t scratch_len, float* rows_out,
+                          void* stream) {
+  const int64_t need = satrl_ppo_diagnostics_scratch(n);
+  if (!valid_h(H) || need < 0 || !src || !P || !sums || !scratch || scratch_len < need) {
+    g_err = "satrl_ppo_diagnostics: H " + std::to_string(H) + ", n " + std::to_string(n) + ", scratch " +
+            std::to_string(scratch_len) + " of " + std::to_string(need) + " f64, or a NULL src / P / sums / scratch";
+    return -1;
+  }
+  const int64_t nrb = (n + kPolRows - 1) / kPolRows;
+  const dim3 g((unsigned)(2 * nrb));
+  hipStream_t s = (hipStream_t)stream;
+  if (H == 64)
+    hipLaunchKernelGGL((diag_kernel<64, 4>), g, dim3(256), 0, s, (int)n, src, idx, P, epsilon, max_action, scratch,
+                       rows_out);
+  else if (H == 128)
+    hipLaunchKernelGGL((diag_kernel<128, 8>), g, dim3(512), 0, s, (int)n, src, idx, P, epsilon, max_action, scratch,
+                       rows_out);
+  else
+    hipLaunchKernelGGL((diag_kernel<256, kPolNW>), g, dim3(kPolNW * 64), 0, s, (int)n, src, idx, P, epsilon,
+                       max_action, scratch, rows_out);
+  LAUNCH_CHECK();
+  const double* lines = scratch;
+  int64_t nl = nrb;
+  if (nrb > kDiagChunk) {                                          // first level: a line per chunk of blocks
+    double* l1 = scratch + nrb * kDiagLine;
+    nl = (nrb + kDiagChunk - 1) / kDiagChunk;
+    hipLaunchKernelGGL(diag_reduce_kernel, dim3((unsigned)nl), dim3(1024), 0, s, lines, nrb, kDiagChunk, l1, 0);
+    LAUNCH_CHECK();
+    lines = l1;
+  }
+  hipLaunchKernelGGL(diag_reduce_kernel, dim3(1), dim3(1024), 0, s, lines, nl, (int)nl, sums, 1);
   LAUNCH_CHECK();
   return 0;
 }

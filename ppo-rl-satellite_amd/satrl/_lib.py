@@ -150,6 +150,9 @@ _SIGS = {
     "satrl_policy_eval": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_int, C.c_uint64, _i64, C.c_uint64, _vp, _vp,
                            _vp, _vp], C.c_int),
     "satrl_policy_value": ([C.c_int, _i64, _vp, _vp, _vp, _vp], C.c_int),
+    "satrl_ppo_diagnostics_scratch": ([_i64], _i64),
+    "satrl_ppo_diagnostics": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _i64, _vp, _vp],
+                              C.c_int),
     "satrl_ppo_stage": ([_i64, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "satrl_ppo_group_advance": ([_vp, _vp], C.c_int),
     "satrl_ppo_tanh": ([_i64, _vp, _vp, _vp], C.c_int),

@@ -108,6 +108,15 @@ def sum_(t: torch.Tensor, pg) -> torch.Tensor:
     return out
 
 
+def max_(t: torch.Tensor, pg) -> torch.Tensor:
+    """Element-wise maximum over ranks (returns a new tensor)."""
+    out = t.clone()
+    if pg is not None:
+        import torch.distributed as dist
+        dist.all_reduce(out, op=dist.ReduceOp.MAX, group=pg)
+    return out
+
+
 def dp_timeout_s() -> float:
     """Host deadline of one watched stretch of collectives (SATRL_DP_TIMEOUT_S,
     default 600 s)."""

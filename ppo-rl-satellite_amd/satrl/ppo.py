@@ -203,6 +203,96 @@ def policy_value(H, obs, P, v_out):
     return v_out
 
 
+DIAG_SLOTS = ["rows", "surr", "kl", "log_ratio", "clipped", "ratio_max", "verr2", "verr", "vt", "vt2"]
+DIAG_MAX_SLOT = DIAG_SLOTS.index("ratio_max")               # the one slot that is a max, not a sum
+
+
+def diagnostics_scratch(n):
+    """f64 elements of ppo_diagnostics' scratch for n rows (satrl_ppo_diagnostics_scratch)."""
+    k = int(_lib.lib().satrl_ppo_diagnostics_scratch(int(n)))
+    if k <= 0:
+        raise ValueError(f"satrl_ppo_diagnostics_scratch({n}) failed")
+    return k
+
+
+def ppo_diagnostics(H, src, idx, P, epsilon, max_action, sums, scratch, rows_out=None):
+    """The update-diagnostics sums (satrl_ppo_diagnostics, include/satrl_ppo.h)
+    of the flat parameters P over rows src[idx] of the packed table (idx None:
+    every row of src) into sums f64 [10] (DIAG_SLOTS); rows_out (optional) f32
+    [n, 4] receives ratio, log ratio, v, 0 per row.  Asynchronous."""
+    _lib.require_cuda(src, torch.float32, (src.shape[0], 32), "src")
+    n = src.shape[0]
+    if idx is not None:
+        n = idx.numel()
+        _lib.require_cuda(idx, torch.int64, (n,), "idx")
+    _lib.require_cuda(P, torch.float32, None, "P")
+    _lib.require_cuda(sums, torch.float64, (len(DIAG_SLOTS),), "sums")
+    _lib.require_cuda(scratch, torch.float64, None, "scratch")
+    if rows_out is not None:
+        _lib.require_cuda(rows_out, torch.float32, None, "rows_out")
+        if rows_out.dim() != 2 or rows_out.shape[0] < n or rows_out.shape[1] != 4:
+            raise _lib.NativeError(f"rows_out shape {tuple(rows_out.shape)} holds fewer than {n} rows of 4")
+    check(_lib.lib().satrl_ppo_diagnostics(int(H), n, ptr(src), ptr(idx), ptr(P), float(epsilon), float(max_action),
+                                           ptr(sums), ptr(scratch), scratch.numel(), ptr(rows_out), stream_ptr()),
+          "satrl_ppo_diagnostics")
+    return sums
+
+
+def reduce_diagnostics_sums(sums, pg):
+    """The diagnostics sums of every rank's rows as one set (a new tensor,
+    equal bits on every rank): the additive slots summed, the max slot maxed."""
+    if pg is None:
+        return sums.clone()
+    out = _dist.sum_(sums, pg)
+    out[DIAG_MAX_SLOT] = _dist.max_(sums[DIAG_MAX_SLOT:DIAG_MAX_SLOT + 1], pg)[0]
+    return out
+
+
+class UpdateDiagnostics:
+    """What an update did, from the sums of satrl_ppo_diagnostics (a pure
+    function of them: no GPU).  Every field is over the whole set of rows the
+    sums cover, under the parameters at the time of the call:
+      rows, policy_loss (-mean min(surr1, surr2)), entropy (state-independent:
+      from log_std), actor_loss (policy_loss - entropy_coef * entropy),
+      value_loss (mean (v - vt)^2, mse_loss), approx_kl (mean (ratio - 1) -
+      log ratio), mean_log_ratio, clip_fraction, ratio_max,
+      explained_variance_after (1 - Var(vt - v) / Var(vt), population
+      variances; NaN when Var(vt) = 0)."""
+
+    FIELDS = ("rows", "policy_loss", "entropy", "actor_loss", "value_loss", "approx_kl", "mean_log_ratio",
+              "clip_fraction", "ratio_max", "explained_variance_after")
+
+    def __init__(self, sums, **fields):
+        self.sums = sums
+        for k in self.FIELDS:
+            setattr(self, k, fields[k])
+
+    @classmethod
+    def from_sums(cls, sums, log_std, entropy_coef):
+        sums = np.array(sums, dtype=np.float64).reshape(-1)
+        if sums.shape[0] != len(DIAG_SLOTS):
+            raise ValueError(f"{len(DIAG_SLOTS)} sums expected, got {sums.shape[0]}")
+        s = {k: float(v) for k, v in zip(DIAG_SLOTS, sums)}
+        n = s["rows"]
+        if not n > 0:
+            raise ValueError("diagnostics over no rows")
+        entropy = float(sum(float(x) for x in np.asarray(log_std, dtype=np.float64).reshape(-1))) + 3 * ENT_CONST
+        policy_loss = -s["surr"] / n
+        var_vt = s["vt2"] / n - (s["vt"] / n) ** 2
+        var_err = s["verr2"] / n - (s["verr"] / n) ** 2
+        return cls(sums, rows=int(n), policy_loss=policy_loss, entropy=entropy,
+                   actor_loss=policy_loss - float(entropy_coef) * entropy, value_loss=s["verr2"] / n,
+                   approx_kl=s["kl"] / n, mean_log_ratio=s["log_ratio"] / n, clip_fraction=s["clipped"] / n,
+                   ratio_max=s["ratio_max"],
+                   explained_variance_after=1.0 - var_err / var_vt if var_vt > 0 else float("nan"))
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    def __repr__(self):
+        return "UpdateDiagnostics(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS) + ")"
+
+
 def moments(x, out=None):
     out = torch.zeros(2, dtype=torch.float64, device=x.device) if out is None else out
     x = x.reshape(-1)
@@ -731,6 +821,7 @@ class PPOLearner:
                 view.copy_(getattr(mod, name).detach())
                 _bind(mod, name, view)
         self._steppers = {}
+        self._diag = None                                    # diagnostics(): (sums, scratch), on first use
 
     # -- lr ---------------------------------------------------------------------
     def lr_decay(self, total_steps):
@@ -799,9 +890,40 @@ class PPOLearner:
         mean, std = _dist.global_mean_std(torch.cat([moments(adv), cnt]), self.pg)
         return (adv - mean.float()) / (std.float() + 1e-5)
 
-    def update_packed(self, src, total_steps, perms=None, generator=None):
+    def diagnostics_sums(self, src, idx=None, rows_out=None):
+        """satrl_ppo_diagnostics of the current parameters over src[idx] (idx
+        None: every row): the f64 [10] device sums (DIAG_SLOTS), a buffer of
+        the learner's own that the next call overwrites.  No host sync."""
+        n = src.shape[0] if idx is None else idx.numel()
+        need = diagnostics_scratch(n)
+        if self._diag is None or self._diag[1].numel() < need:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            self._diag = (torch.zeros(len(DIAG_SLOTS), **f64), torch.empty(need, **f64))
+        sums, scratch = self._diag
+        return ppo_diagnostics(self.H, src, idx, self.P, self.epsilon, self.max_action, sums, scratch, rows_out)
+
+    def diagnostics_from(self, sums):
+        """UpdateDiagnostics of host or device sums under the current log_std."""
+        if torch.is_tensor(sums):
+            sums = sums.cpu().numpy()
+        o = self.off["ls"]
+        return UpdateDiagnostics.from_sums(sums, self.P[o:o + 3].cpu().numpy(), self.entropy_coef)
+
+    def diagnostics(self, src, idx=None, rows_out=None):
+        """What the current parameters make of the packed rows src[idx] (idx
+        None: every row) as an UpdateDiagnostics: the forward pass is the fused
+        update's own (satrl_ppo_diagnostics), nothing of the learner changes.
+        rows_out (optional) f32 [n, 4] receives ratio, log ratio, v, 0 per row.
+        Reads the ten sums back (one host sync)."""
+        return self.diagnostics_from(self.diagnostics_sums(src, idx, rows_out))
+
+    def update_packed(self, src, total_steps, perms=None, generator=None, after_epoch=None):
         """K epochs of minibatch steps over the packed table src [B, 32]
-        (adv already normalised), then lr decay (ppo_continuous.py:212-242)."""
+        (adv already normalised), then lr decay (ppo_continuous.py:212-242).
+        after_epoch (optional): after_epoch(ep, perm) runs after epoch ep's
+        minibatches; a true return ends the epoch loop there (the permutations
+        of the epochs not run are then never drawn).  The checks and the lr
+        decay below run either way."""
         B = src.shape[0]
         self.sync_w2t()
         st = self.stepper(min(self.mini_batch_size, B))
@@ -811,6 +933,8 @@ class PPOLearner:
             else:
                 perm = perms(ep) if callable(perms) else perms[ep]     # a callable draws each epoch's order lazily
             st.run(src, perm)
+            if after_epoch is not None and after_epoch(ep, perm):
+                break
         if self.peer is not None:
             self.peer.check()                # a peer's value never arrived: the update is invalid
         if uses_column_split(self.H, self.mini_batch_size, B):

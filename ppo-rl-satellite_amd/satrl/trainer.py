@@ -14,7 +14,9 @@
   and gradients are averaged with RCCL.  Opt-in (obs_norm, reward_scaling):
   running observation normalisation and reward scaling, satrl/norm.py.
   ``VecTrainer.evaluate`` measures the current policies on a fresh env handle
-  without touching any training state, satrl/evaluate.py.
+  without touching any training state, satrl/evaluate.py.  Opt-in
+  (diagnostics, target_kl): per-update loss / KL / clip-fraction figures in
+  ``VecTrainer.diagnostics`` and the KL early stop of an update's epochs.
 """
 from __future__ import annotations
 
@@ -27,7 +29,8 @@ from . import dist as _dist
 from . import norm as _norm
 from .buffer import ReplayBuffer, RolloutBuffer
 from .env import VecSatellites
-from .ppo import PPO_continuous, PPOLearner, gae, gaussian_sample, policy_act, policy_value
+from .ppo import (PPO_continuous, PPOLearner, gae, gaussian_sample, moments, policy_act, policy_value,
+                  reduce_diagnostics_sums)
 
 
 class args_param:  # noqa: N801
@@ -41,7 +44,8 @@ class args_param:  # noqa: N801
                  chkpt_dir="/mnt/datab/home/yuanwenzheng/PICTURE1",
                  num_envs=1, horizon=None, seed=0, rollout_graph_chunk=64, update_graph_group=64, device=None,
                  surrogate=False, dp_minibatch="global", minibatch_sampler=None, allreduce="rccl",
-                 obs_norm=False, reward_scaling=False, obs_clip=10.0, obs_norm_calib_steps=64):
+                 obs_norm=False, reward_scaling=False, obs_clip=10.0, obs_norm_calib_steps=64,
+                 diagnostics=False, diagnostics_rows=None, target_kl=None):
         self.max_train_steps = max_train_steps
         self.evaluate_freq = evaluate_freq
         self.save_freq = save_freq
@@ -111,6 +115,16 @@ class args_param:  # noqa: N801
         self.reward_scaling = reward_scaling
         self.obs_clip = obs_clip
         self.obs_norm_calib_steps = obs_norm_calib_steps
+        # update diagnostics of the vectorised engine (VecTrainer.diagnostics: policy /
+        # value loss, entropy, approximate KL, clip fraction, explained variance),
+        # measured by a forward pass over the table after the update's last epoch;
+        # diagnostics_rows: over the first that many rows of that epoch's
+        # permutation instead of the whole table.  target_kl: measured after
+        # every epoch, and the update's remaining epochs are skipped once
+        # approx_kl > target_kl (implies diagnostics)
+        self.diagnostics = diagnostics
+        self.diagnostics_rows = diagnostics_rows
+        self.target_kl = target_kl
         # set by the train_* functions from the env (CPPO_main.py:99-101)
         self.state_dim = 18
         self.action_dim = 3
@@ -319,6 +333,16 @@ class VecTrainer:
         self.episodes = 0.0
         self.evaluations = []                                # train(evaluate_every=...): (iteration, episodes, summary)
         self._evaluators = {}                                # evaluate(): one cached VecEvaluator per num_envs
+        tkl = getattr(args, "target_kl", None)
+        self.target_kl = None if tkl is None else float(tkl)
+        self.diagnostics_on = bool(getattr(args, "diagnostics", False)) or self.target_kl is not None
+        rows = getattr(args, "diagnostics_rows", None)
+        self.diagnostics_rows = None if rows is None else int(rows)
+        if self.diagnostics_rows is not None and not 0 < self.diagnostics_rows <= self.T * self.N:
+            raise ValueError(f"diagnostics_rows must be in 1..{self.T * self.N} (the local table), "
+                             f"got {self.diagnostics_rows}")
+        self.diagnostics = []                                # update(): one dict per update when diagnostics are on
+        self.last_diagnostics = None
         self.surrogate = None
         self.ellipse_params = None
         if getattr(args, "surrogate", False):
@@ -607,7 +631,53 @@ class VecTrainer:
         return self.rew_s
 
     def update(self):
-        self.learner.update_packed(self.buf.packed, self.episodes, perms=lambda ep: self.epoch_perm())
+        if not self.diagnostics_on:
+            self.learner.update_packed(self.buf.packed, self.episodes, perms=lambda ep: self.epoch_perm())
+            return
+        self._update_with_diagnostics()
+
+    def _explained_variance(self):
+        """The pre-update 1 - Var(v_target - V_old) / Var(v_target) over every
+        rank's rows (population variances; buf.adv is the raw advantage
+        v_target - V_old); NaN when Var(v_target) = 0."""
+        buf = self.buf
+        n = torch.tensor([float(buf.adv.numel())], dtype=torch.float64, device=self.device)
+        m = _dist.sum_(torch.cat([moments(buf.adv), moments(buf.vtarget), n]), self.pg).cpu().tolist()
+        var_adv = m[1] / m[4] - (m[0] / m[4]) ** 2
+        var_vt = m[3] / m[4] - (m[2] / m[4]) ** 2
+        return 1.0 - var_adv / var_vt if var_vt > 0 else float("nan")
+
+    def _update_with_diagnostics(self):
+        """update() with args.diagnostics / target_kl: the same minibatch
+        steps, and after the last epoch run (with target_kl: after every epoch)
+        learner.diagnostics over the table, or over the first diagnostics_rows
+        rows of that epoch's permutation.  These are whole-set figures under
+        the parameters after the epoch, not means over the minibatches during
+        it.  With target_kl the epoch loop ends once approx_kl > target_kl (the
+        plain comparison); the epochs not run draw no permutation, so the
+        minibatch generator is then left in an earlier state than a full update
+        leaves it.  Under a process group the sums are reduced over the ranks
+        first: every rank records and decides the same.  Appends a dict to
+        self.diagnostics; touches nothing the training reads."""
+        L, buf = self.learner, self.buf
+        ev_before = self._explained_variance()
+        state = {"epochs": 0, "diag": None}
+
+        def after_epoch(ep, perm):
+            state["epochs"] = ep + 1
+            if self.target_kl is None and ep + 1 < L.K_epochs:
+                return False
+            idx = None if self.diagnostics_rows is None else perm[:self.diagnostics_rows]
+            sums = reduce_diagnostics_sums(L.diagnostics_sums(buf.packed, idx), self.pg)
+            state["diag"] = L.diagnostics_from(sums)
+            return self.target_kl is not None and state["diag"].approx_kl > self.target_kl
+
+        L.update_packed(buf.packed, self.episodes, perms=lambda ep: self.epoch_perm(), after_epoch=after_epoch)
+        rec = {"iteration_count": self.iteration_count, "episodes": self.episodes, "epochs_run": state["epochs"],
+               "explained_variance": ev_before}
+        rec.update(state["diag"].as_dict())
+        self.diagnostics.append(rec)
+        self.last_diagnostics = rec
 
     def finish_iteration(self):
         # next rollout starts from the current observation
