@@ -1098,14 +1098,18 @@ __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* 
 }
 
 template <int H, int NW, int R = kRows, bool FDW2 = false, bool KX = false, bool SPAN = false>
-__global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb, const float* __restrict__ src,
-                                                      const int64_t* __restrict__ idx, const float* __restrict__ P,
-                                                      const void* __restrict__ W2X, float epsilon, float ent_coef,
-                                                      float max_action, float* __restrict__ H1g,
-                                                      float* __restrict__ dZ2g, float* __restrict__ ptail,
-                                                      float* __restrict__ pw1, int net_sel, float* __restrict__ p2,
+__global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb, int net_sel,
+                                                      const float* __restrict__ src, const int64_t* __restrict__ idx,
+                                                      const float* __restrict__ P, const void* __restrict__ W2X,
+                                                      float* __restrict__ H1g,
+                                                      float* __restrict__ dZ2g, float epsilon, float ent_coef,
+                                                      float max_action, float* __restrict__ ptail,
+                                                      float* __restrict__ pw1, float* __restrict__ p2,
                                                       int S2, float* __restrict__ ratio_out, float inv_mb,
                                                       unsigned long long* __restrict__ span) {
+  // (argument order: the 14 dwords up to dZ2g are preloaded into SGPRs at wave
+  // launch -- everything the block's net, the first weight loads and the row
+  // gather need; the rest comes by s_load under them.  DESIGN.md 3.4)
   const unsigned long long span_t0 = SPAN ? satrl_span::now() : 0ull;   // (SPAN: the measurement instantiation)
   constexpr int RT = R / 16, LDA = H + 4, CT = H / 16 / NW, NT = NW * 64;
   static_assert(!FDW2 || R == 32, "the fused dW2 partial covers one 32-row block (dw2_kernel's chunk)");
@@ -2240,12 +2244,17 @@ __device__ __forceinline__ void reduce_block(int H, const Layout& L, const RedGe
 }
 
 template <bool SPAN = false>
-__global__ void __launch_bounds__(256) reduce_kernel(int H, RedGeom g, int mode, const float* __restrict__ p2,
+__global__ void __launch_bounds__(256) reduce_kernel(int H, int mode, int nb2, int S, int net_sel, int ch2,
+                                                     const float* __restrict__ p2, double* __restrict__ steps,
+                                                     float* __restrict__ G, double* __restrict__ nsq, RedGeom g,
                                                      const float* __restrict__ p1, const float* __restrict__ pt,
-                                                     float* __restrict__ G, double* __restrict__ nsq,
-                                                     double* __restrict__ steps, int world,
-                                                     unsigned long long* __restrict__ span) {
+                                                     int world, unsigned long long* __restrict__ span) {
   const unsigned long long span_t0 = SPAN ? satrl_span::now() : 0ull;
+  // (argument order: the 14 dwords up to nsq are preloaded.  A by-value struct
+  // is never preloaded, so what a W2 block -- every block of the update's
+  // reduce launch -- reads of the geometry comes as scalars ahead of it, and
+  // g's copies of them are replaced: its slab loads wait for no s_load)
+  g.nb2 = nb2; g.S = S; g.net = net_sel; g.ch2 = ch2;
   const Layout L = layout(H);
   __shared__ double sh[8];
   __shared__ float4 red[256];
@@ -2287,6 +2296,9 @@ __global__ void __launch_bounds__(256) dw2_kx_w1_kernel(int mb, int S, int KR, i
                                                         int ndw, RedGeom g, int mode, const float* __restrict__ p1,
                                                         const float* __restrict__ pt, float* __restrict__ G,
                                                         double* __restrict__ nsq, unsigned long long* __restrict__ span) {
+  // (argument order: the 11 dwords up to ndw are preloaded -- all a dW2
+  // block's plane stream needs; a by-value struct ends the preloaded run, and
+  // the few reduce blocks behind it run beside the stream, off its path)
   const unsigned long long span_t0 = SPAN ? satrl_span::now() : 0ull;
   __shared__ __attribute__((aligned(16))) KxSmem<TW> sm;
   if ((int)blockIdx.x < ndw) {
@@ -2359,13 +2371,14 @@ __device__ __forceinline__ float adam_elem(float g, float& m, float& v, float p,
 
 template <bool SPAN = false>
 __global__ void __launch_bounds__(256) adam_kernel(int H, int nblk, const double* __restrict__ nsq,
-                                                   const double* __restrict__ steps, const double* __restrict__ bct,
-                                                   int bct_len, const float* __restrict__ lr, float beta1,
-                                                   float beta2, float eps, float max_norm, int use_clip,
                                                    const float* __restrict__ G, float* __restrict__ P,
-                                                   float* __restrict__ M, float* __restrict__ V,
-                                                   void* __restrict__ W2X, int net_sel,
-                                                   unsigned long long* __restrict__ span) {
+                                                   float* __restrict__ M, float* __restrict__ V, int net_sel,
+                                                   int bct_len, const double* __restrict__ steps,
+                                                   const double* __restrict__ bct, const float* __restrict__ lr,
+                                                   float beta1, float beta2, float eps, float max_norm, int use_clip,
+                                                   void* __restrict__ W2X, unsigned long long* __restrict__ span) {
+  // (argument order: the 14 dwords up to bct_len are preloaded -- the norm
+  // partials' and the G / M / V / P loads below need nothing else)
   const unsigned long long span_t0 = SPAN ? satrl_span::now() : 0ull;
   const Layout L = layout(H);
   __shared__ double sh[8];
@@ -2821,8 +2834,8 @@ static int launch_rowpass(int H, int mb, int net, const float* src, const int64_
   unsigned long long* sp =
       satrl_span::take(satrl_span::kRowpass, cs ? (int64_t)gc.x * kCsWaves : (int64_t)g.x * nw);
   auto rp = [&](auto k) {
-    launch_span(k.first, k.second, sp, g, dim3(nw * 64), stream, mb, src, idx, P, W2X, epsilon, ent_coef, max_action,
-                H1, dZ2, ptail, pw1, net, p2, nrb, ratio, inv_mb);
+    launch_span(k.first, k.second, sp, g, dim3(nw * 64), stream, mb, net, src, idx, P, W2X, H1, dZ2, epsilon,
+                ent_coef, max_action, ptail, pw1, p2, nrb, ratio, inv_mb);
   };
   if (H == 64 && fdw2)
     rp(rowpass_k<64, 4, kRows, true, false>());
@@ -3036,8 +3049,8 @@ int satrl_ppo_reduce(int H, int mb, int net, int S, int mode, const float* p2, i
   const RedGeom g = geom(H, mb, S, net);
   const int nb = w2_only ? g.nb2 : n_blocks(g);
   unsigned long long* sp = satrl_span::take(satrl_span::kReduce, (int64_t)nb * 4);
-  launch_span(reduce_kernel<true>, reduce_kernel<false>, sp, dim3(nb), dim3(256), stream, H, g, mode, p2, p1, pt, G,
-              nsq, steps, 1);
+  launch_span(reduce_kernel<true>, reduce_kernel<false>, sp, dim3(nb), dim3(256), stream, H, mode, g.nb2, g.S,
+              g.net, g.ch2, p2, steps, G, nsq, g, p1, pt, 1);
   LAUNCH_CHECK();
   return 0;
 }
@@ -3045,8 +3058,8 @@ int satrl_ppo_reduce(int H, int mb, int net, int S, int mode, const float* p2, i
 int satrl_ppo_reduce_dp(int H, int mb, int net, int world, float* G, double* nsq, double* steps, void* stream) {
   if (!valid_h(H) || mb <= 0 || net < -1 || net > 1 || world < 1 || !G || !nsq || !steps) return -1;
   const RedGeom g = geom(H, mb, 1, net);
-  hipLaunchKernelGGL(reduce_kernel<false>, dim3(n_blocks(g)), dim3(256), 0, (hipStream_t)stream, H, g, 2, nullptr,
-                     nullptr, nullptr, G, nsq, steps, world, nullptr);
+  hipLaunchKernelGGL(reduce_kernel<false>, dim3(n_blocks(g)), dim3(256), 0, (hipStream_t)stream, H, 2, g.nb2, g.S,
+                     g.net, g.ch2, nullptr, steps, G, nsq, g, nullptr, nullptr, world, nullptr);
   LAUNCH_CHECK();
   return 0;
 }
@@ -3162,7 +3175,7 @@ int satrl_ppo_adam(int H, int mb, int net, const double* nsq, const double* step
   const int nblk = n_blocks(geom(H, mb, 1, net));
   unsigned long long* sp = satrl_span::take(satrl_span::kAdam, (int64_t)n_adam_blocks(H, net) * 4);
   launch_span(adam_kernel<true>, adam_kernel<false>, sp, dim3(n_adam_blocks(H, net)), dim3(256), stream, H, nblk, nsq,
-              steps, bct, bct_len, lr, beta1, beta2, eps, max_norm, use_clip, G, P, M, V, W2X, net);
+              G, P, M, V, net, bct_len, steps, bct, lr, beta1, beta2, eps, max_norm, use_clip, W2X);
   LAUNCH_CHECK();
   return 0;
 }
