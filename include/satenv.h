@@ -123,6 +123,56 @@ int satenv_step_autoreset(satenv_env* h, const float* pa, const float* ea, float
 int satenv_get_state(const satenv_env* h, double* f64_planes, int32_t* i32_planes, void* stream);
 int satenv_set_state(satenv_env* h, const double* f64_planes, const int32_t* i32_planes, void* stream);
 
+/* Randomised episode starts (no reference counterpart: the reference's
+ * reset() is one fixed point, and that stays the default).  A handle carries
+ * a reset distribution, a uniform box over the 12 kinematic scalars in
+ * init_kin order.  While it is enabled, every reset of env i -- the masked
+ * satenv_reset and the reset inside satenv_step_autoreset -- starts from
+ *   k[c] = lo[c] + (hi[c] - lo[c]) * u,   u = (w[c] + 0.5) * 2^-32 in (0, 1),
+ * w = the 12 words of Philox4x32-10 blocks j = 0, 1, 2 with counter
+ * (lo32(gid), hi32(gid), ep, j), gid = env_offset + i, ep = the env's episode
+ * index before the reset, keyed by (seed, stream 2) as the action noise is
+ * by (seed, agent 0 / 1).  So the starts depend on (seed, global env id,
+ * episode index) alone: the same for every step kernel, for the host build
+ * (bit for bit) and for every sharding of the envs over handles.  Such a
+ * reset leaves float velocities (bits [4] = 0); there is no rejection, a
+ * start inside d_capture is captured on its first step.  Disabled, a reset
+ * is the reference's.
+ * The episode index is an int32 per env, 0 at create and advanced by every
+ * reset of that env, enabled or not; it is not part of get/set_state.
+ * satenv_set_reset_dist copies *host into the handle's device block with a
+ * stream-ordered kernel: it takes effect for the launches after it on
+ * `stream`, replays of graphs captured earlier included (no recapture).
+ * One exception: the step kernels that can draw are instantiations of their
+ * own, so that a handle which never enables a distribution launches exactly
+ * the kernels it did before; the first enabling call switches the handle
+ * to them for good (they read `enabled` from the block).  A graph captured
+ * BEFORE a handle's first enabling call therefore keeps the fixed reset and
+ * has to be captured again; every later change, disabling included, needs
+ * no recapture.
+ * Null pointers, non-finite bounds and lo > hi return SATENV_ERR_ARG.        */
+typedef struct satenv_reset_dist {
+    double   lo[12], hi[12];   /* Pp Pv Ep Ev, metres and m/s, lo <= hi, finite */
+    uint64_t seed;
+    int64_t  env_offset;       /* global env id of env 0 (data-parallel shards) */
+    int32_t  enabled;          /* 0: the reference's fixed reset */
+    int32_t  reserved;
+} satenv_reset_dist;
+int satenv_default_reset_dist(satenv_reset_dist* host);   /* lo = hi = the reset's constants, enabled 0 */
+int satenv_set_reset_dist(satenv_env* h, const satenv_reset_dist* host, void* stream);
+int satenv_get_reset_dist(const satenv_env* h, satenv_reset_dist* host);
+int satenv_get_episode_index(const satenv_env* h, int32_t* out /* device [N] */, void* stream);
+int satenv_set_episode_index(satenv_env* h, const int32_t* in /* device [N], NULL = zeros */, void* stream);
+/* The same five on the host build's handle (satenv_cpu.h, which includes this
+ * header; host pointers, synchronous): declared here, next to the struct
+ * and the contract they share.                                             */
+struct satenv_cpu_env;
+int satenv_cpu_default_reset_dist(satenv_reset_dist* host);
+int satenv_cpu_set_reset_dist(struct satenv_cpu_env* h, const satenv_reset_dist* host, void* stream);
+int satenv_cpu_get_reset_dist(const struct satenv_cpu_env* h, satenv_reset_dist* host);
+int satenv_cpu_get_episode_index(const struct satenv_cpu_env* h, int32_t* out, void* stream);
+int satenv_cpu_set_episode_index(struct satenv_cpu_env* h, const int32_t* in, void* stream);
+
 /* Time_window_of_danger_zone(R0_c, V0_c, R0_t, V0_t, Delta_V_c=fuel)
  *   .calculate_number_of_hanger_area()   satellite_function.py:18-99,341-373
  * on n independent absolute states: states f64 [n][12] = R_c V_c R_t V_t,

@@ -7,33 +7,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int rnd = 0; rnd < 10; ++rnd) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = (uint32_t)p1;
-    c[2] = n2;
-    c[3] = (uint32_t)p0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
+#include "philox_core.h"   // philox4x32_10, philox_key
 
 __device__ __forceinline__ float philox_u01_open0(uint32_t x) {   // (0, 1]
   return ((float)(x >> 8) + 1.0f) * (1.0f / 16777216.0f);
 }
 __device__ __forceinline__ float philox_u01(uint32_t x) {         // [0, 1)
   return (float)(x >> 8) * (1.0f / 16777216.0f);
-}
-
-// key of (seed, agent)
-__host__ __device__ inline void philox_key(uint64_t seed, uint32_t agent, uint32_t& k0, uint32_t& k1) {
-  k0 = (uint32_t)seed ^ (agent * 0x85EBCA6Bu);
-  k1 = (uint32_t)(seed >> 32) ^ (agent * 0xC2B2AE35u + 0x27D4EB2Fu);
 }
 
 // four standard normals for (global env id, step)

@@ -3,8 +3,9 @@
 // The env step of the gfx950 kernels, compiled by g++ for host cores: the
 // same satenv_device.h / satenv_step.h source, one loop iteration per env
 // where the kernel has one lane per env, OpenMP over envs.  Same state
-// layout as a device handle (f64 planes [16][N], i32 planes [3][N]), so the
-// get/set_state planes are interchangeable between the two builds.
+// layout as a device handle (f64 planes [16][N], i32 planes [4][N]), so the
+// get/set_state planes are interchangeable between the two builds; the
+// reset distribution and the per-env episode index likewise (satenv.h).
 //
 // Reference (qiaobeibei/PPO-RL-Satellite): environment.py:26-255 (ctor,
 // reset, step Flag 0/1), CPPO_main.py:119-153 (the loop step_autoreset
@@ -41,6 +42,8 @@ struct satenv_cpu_env {
   std::vector<double> f64;
   std::vector<int32_t> i32;
   int32_t err = 0;
+  ResetDist rd{};                   // the reset distribution as the step reads it
+  satenv_reset_dist dist{};         // ... and as satenv_cpu_set_reset_dist was given it
 };
 
 namespace {
@@ -48,7 +51,7 @@ namespace {
 // step_lane for env i; st (may be null) = the four per-env stat planes [4][n]
 void step_env(satenv_cpu_env* h, const StepIO& io, int64_t i, bool autoreset, double* st) {
   StepStats s;
-  const int rc = step_lane<true>(h->prm, h->n, h->f64.data(), h->i32.data(), io, i, autoreset, s);
+  const int rc = step_lane<true, true>(h->prm, h->n, h->f64.data(), h->i32.data(), io, i, autoreset, s);
   if (rc) {
 #pragma omp critical(satenv_cpu_err)
     if (h->err == 0) h->err = rc;
@@ -77,6 +80,8 @@ int satenv_cpu_create(satenv_cpu_env** out, int64_t num_envs, const satenv_param
   h->prm = *p;
   h->f64.assign((size_t)kF64Planes * num_envs, 0.0);
   h->i32.assign((size_t)kI32Planes * num_envs, 0);
+  satenv_cpu_default_reset_dist(&h->dist);
+  reset_dist_pack(h->dist, h->rd);
   for (int64_t i = 0; i < num_envs; ++i) init_env(h->prm, num_envs, h->f64.data(), h->i32.data(), i);
   *out = h;
   return SATENV_OK;
@@ -109,14 +114,14 @@ int satenv_cpu_reset(satenv_cpu_env* h, int32_t flag, const uint8_t* env_mask, f
   h->prm.flag = flag;
 #pragma omp parallel for num_threads(h->threads) schedule(static)
   for (int64_t i = 0; i < h->n; ++i)
-    reset_env(h->prm, h->n, h->f64.data(), h->i32.data(), flag, env_mask, obs_out, obs64_out, i);
+    reset_env(h->prm, &h->rd, h->n, h->f64.data(), h->i32.data(), flag, env_mask, obs_out, obs64_out, i);
   return SATENV_OK;
 }
 
 int satenv_cpu_step(satenv_cpu_env* h, const float* pa, const float* ea, const int32_t* episode_count,
                     float* obs_out, double* obs64_out, double* reward_out, uint8_t* done_out, void* /*stream*/) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_cpu_step: null argument");
-  const StepIO io{pa, ea, episode_count, obs_out, obs64_out, reward_out, nullptr, done_out, nullptr, nullptr};
+  const StepIO io{pa, ea, episode_count, obs_out, obs64_out, reward_out, nullptr, done_out, nullptr, nullptr, &h->rd};
 #pragma omp parallel for num_threads(h->threads) schedule(dynamic, 64)
   for (int64_t i = 0; i < h->n; ++i) step_env(h, io, i, false, nullptr);
   return SATENV_OK;
@@ -125,7 +130,7 @@ int satenv_cpu_step(satenv_cpu_env* h, const float* pa, const float* ea, const i
 int satenv_cpu_step_autoreset(satenv_cpu_env* h, const float* pa, const float* ea, float* obs_out,
                               float* reward_out, uint8_t* done_out, double* stats_out, void* /*stream*/) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_cpu_step_autoreset: null argument");
-  const StepIO io{pa, ea, nullptr, obs_out, nullptr, nullptr, reward_out, done_out, nullptr, nullptr};
+  const StepIO io{pa, ea, nullptr, obs_out, nullptr, nullptr, reward_out, done_out, nullptr, nullptr, &h->rd};
   const int64_t n = h->n;
   std::vector<double> st;
   if (stats_out) st.assign((size_t)4 * n, 0.0);
@@ -153,6 +158,48 @@ int satenv_cpu_set_state(satenv_cpu_env* h, const double* f64_planes, const int3
   if (!h) return fail(SATENV_ERR_ARG, "satenv_cpu_set_state: null handle");
   if (f64_planes) std::memcpy(h->f64.data(), f64_planes, sizeof(double) * SATENV_F64_PLANES * h->n);
   if (i32_planes) std::memcpy(h->i32.data(), i32_planes, sizeof(int32_t) * SATENV_I32_PLANES * h->n);
+  return SATENV_OK;
+}
+
+int satenv_cpu_default_reset_dist(satenv_reset_dist* d) {
+  if (!d) return fail(SATENV_ERR_ARG, "satenv_cpu_default_reset_dist: null");
+  std::memset(d, 0, sizeof(*d));
+  double k[12];
+  reset_kin(satenv_params{}, k);
+  std::memcpy(d->lo, k, sizeof(k));
+  std::memcpy(d->hi, k, sizeof(k));
+  return SATENV_OK;
+}
+
+int satenv_cpu_set_reset_dist(satenv_cpu_env* h, const satenv_reset_dist* d, void* /*stream*/) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_cpu_set_reset_dist: null argument");
+  ResetDist rd;
+  if (!reset_dist_pack(*d, rd))
+    return fail(SATENV_ERR_ARG, "satenv_cpu_set_reset_dist: bounds must be finite, lo <= hi");
+  h->rd = rd;
+  h->dist = *d;
+  h->dist.enabled = d->enabled != 0;
+  h->dist.reserved = 0;
+  return SATENV_OK;
+}
+
+int satenv_cpu_get_reset_dist(const satenv_cpu_env* h, satenv_reset_dist* d) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_cpu_get_reset_dist: null argument");
+  *d = h->dist;
+  return SATENV_OK;
+}
+
+int satenv_cpu_get_episode_index(const satenv_cpu_env* h, int32_t* out, void* /*stream*/) {
+  if (!h || !out) return fail(SATENV_ERR_ARG, "satenv_cpu_get_episode_index: null argument");
+  std::memcpy(out, h->i32.data() + (size_t)kPlaneEp * h->n, sizeof(int32_t) * h->n);
+  return SATENV_OK;
+}
+
+int satenv_cpu_set_episode_index(satenv_cpu_env* h, const int32_t* in, void* /*stream*/) {
+  if (!h) return fail(SATENV_ERR_ARG, "satenv_cpu_set_episode_index: null handle");
+  int32_t* dst = h->i32.data() + (size_t)kPlaneEp * h->n;
+  if (in) std::memcpy(dst, in, sizeof(int32_t) * h->n);
+  else std::memset(dst, 0, sizeof(int32_t) * h->n);
   return SATENV_OK;
 }
 

@@ -2,7 +2,7 @@
 //
 // Layout in HBM (per handle, num_envs = N):
 //   f64 planes [16][N]  Pp0..2 Pv0..2 Ep0..2 Ev0..2 fuel_c fuel_t dis ep_return
-//   i32 planes [3][N]   dangerous_zone, episode_count, bits
+//   i32 planes [4][N]   dangerous_zone, episode_count, bits, episode index
 // One lane per env; every plane access is a unit-stride (coalesced) 8-/4-B
 // load/store.  Actions [N][3] f32 and obs [N][18] f32 are row-major as the
 // policy GEMMs consume them.  The STM and scalars ride in the kernel's
@@ -71,14 +71,16 @@ __device__ __forceinline__ void wave_stats(double* stats, StepStats s) {
 }
 
 // The step kernels share one signature (launch_step); only a SPAN instantiation uses its last argument.
+// DRAW: the autoreset draws the start from the handle's reset distribution (satenv_step.h reset_state);
+// the default instantiations, which handles that never enabled one launch, do not carry that code.
 // One lane per env, the count's four solves one after another (64-lane blocks):
-template <bool AUTORESET, bool RK45 = false>
+template <bool AUTORESET, bool RK45 = false, bool DRAW = false>
 __global__ void __launch_bounds__(64) step_kernel(const Params prm, int64_t n, double* __restrict__ f64,
                                                   int32_t* __restrict__ i32, StepIO io, unsigned long long*) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   StepStats s;
   if (i < n) {
-    const int rc = step_lane<RK45>(prm, n, f64, i32, io, i, AUTORESET, s);
+    const int rc = step_lane<RK45, DRAW>(prm, n, f64, i32, io, i, AUTORESET, s);
     if (rc) atomicCAS(io.err, 0, rc);
   }
   if (io.stats) wave_stats(io.stats, s);
@@ -106,7 +108,7 @@ __device__ __forceinline__ bool lane_head(const Params& prm, int64_t n, const do
 // latency bound: 16384 envs are only 256 waves).  Bit-identical to
 // step_kernel: every problem runs the same hybrd1.
 constexpr int kSplitEnvs = 64;
-template <bool AUTORESET, bool RK45 = false>
+template <bool AUTORESET, bool RK45 = false, bool DRAW = false>
 __global__ void __launch_bounds__(256) step_kernel_split(const Params prm, int64_t n, double* __restrict__ f64,
                                                          int32_t* __restrict__ i32, StepIO io, unsigned long long*) {
   __shared__ double sA[4][kSplitEnvs], sSt[4][kSplitEnvs], sDvm[4][kSplitEnvs], sX[4][kSplitEnvs];
@@ -154,7 +156,7 @@ __global__ void __launch_bounds__(256) step_kernel_split(const Params prm, int64
       }
       step_reward(prm, L, cnt);
     }
-    step_end(prm, n, f64, i32, io, i, AUTORESET, L, s);
+    step_end<DRAW>(prm, n, f64, i32, io, i, AUTORESET, L, s);
   }
   if (w == 0 && io.stats) wave_stats(io.stats, s);
 }
@@ -248,7 +250,7 @@ __device__ __forceinline__ RfSolve get_rf_problem(const WideSmem<E>& sm, int w, 
 // ENVS envs per workgroup (lanes >= ENVS of each wave idle): fewer envs per
 // wave put more waves, i.e. more independent dependency chains, on each SIMD
 // when N is small (the step is latency bound there); 64 at large N
-template <bool AUTORESET, int ENVS, bool SPAN = false>
+template <bool AUTORESET, int ENVS, bool SPAN = false, bool DRAW = false>
 __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_t n, double* __restrict__ f64,
                                                         int32_t* __restrict__ i32, StepIO io,
                                                         unsigned long long* __restrict__ span) {
@@ -355,19 +357,23 @@ __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_
       for (int c = 0; c < 4; ++c) t[c] = sm.rt[c][lane];
       step_reward_terms(prm, L, cnt, t);
     }
-    step_end(prm, n, f64, i32, io, i, AUTORESET, L, s);
+    step_end<DRAW>(prm, n, f64, i32, io, i, AUTORESET, L, s);
   }
   if (w == 0 && io.stats) wave_stats(io.stats, s);
   ENV_PROBE(6);
   if constexpr (SPAN) satrl_span::exit(span, span_t0);
 }
 
-__global__ void __launch_bounds__(256) reset_kernel(const Params prm, int64_t n, double* __restrict__ f64,
-                                                    int32_t* __restrict__ i32, int32_t flag, const uint8_t* mask,
-                                                    float* obs, double* obs64) {
+__global__ void __launch_bounds__(256) reset_kernel(const Params prm, const ResetDist* __restrict__ rd, int64_t n,
+                                                    double* __restrict__ f64, int32_t* __restrict__ i32,
+                                                    int32_t flag, const uint8_t* mask, float* obs, double* obs64) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) reset_env(prm, n, f64, i32, flag, mask, obs, obs64, i);
+  if (i < n) reset_env(prm, rd, n, f64, i32, flag, mask, obs, obs64, i);
 }
+
+// satenv_set_reset_dist: the struct rides in the argument segment, one lane
+// writes it into the handle's block -- stream-ordered with the steps around it
+__global__ void set_reset_dist_kernel(const ResetDist d, ResetDist* __restrict__ dst) { *dst = d; }
 
 __global__ void init_kernel(const Params prm, int64_t n, double* f64, int32_t* i32) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -667,6 +673,9 @@ struct satenv_env {
   double* f64 = nullptr;
   int32_t* i32 = nullptr;
   int32_t* err = nullptr;
+  ResetDist* rd = nullptr;          // the reset distribution as the kernels read it (device)
+  satenv_reset_dist dist{};         // ... and as satenv_set_reset_dist was given it
+  bool draw = false;                // a distribution was enabled once: launch the DRAW step kernels
   int kind = 2;    // step_kernel_wide (2), step_kernel_split (1) or the one-lane step_kernel (0)
   int wide_envs = 64;   // envs per workgroup of the wide kernel (16 / 32 for A/B; fewer envs per
                         // workgroup measured no faster)
@@ -676,27 +685,36 @@ namespace {
 
 int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
-template <bool AR>
-void launch_step(satenv_env* h, const StepIO& io, void* stream) {
-  void (*plain)(const Params, int64_t, double*, int32_t*, StepIO, unsigned long long*) = step_kernel<AR>;
+template <bool AR, bool DRAW>
+void launch_step_draw(satenv_env* h, const StepIO& io, void* stream) {
+  void (*plain)(const Params, int64_t, double*, int32_t*, StepIO, unsigned long long*) = step_kernel<AR, false, DRAW>;
   decltype(plain) probed = nullptr;
   int envs = 64, threads = 256;   // per workgroup
   if (h->prm.propagator == 2) {   // the RK45 instantiation (its registers stay out of the STM kernels)
-    plain = step_kernel_split<AR, true>;
+    plain = step_kernel_split<AR, true, DRAW>;
   } else if (h->kind == 2) {
     envs = h->wide_envs;
-    plain = envs == 16 ? step_kernel_wide<AR, 16> : envs == 32 ? step_kernel_wide<AR, 32> : step_kernel_wide<AR, 64>;
+    plain = envs == 16   ? step_kernel_wide<AR, 16, false, DRAW>
+            : envs == 32 ? step_kernel_wide<AR, 32, false, DRAW>
+                         : step_kernel_wide<AR, 64, false, DRAW>;
     // the product geometry (64 envs per workgroup) has a SPAN instantiation
     // for the bench's live launch spans (span_probe.h)
-    if (envs == 64) probed = step_kernel_wide<AR, 64, true>;
+    if (envs == 64) probed = step_kernel_wide<AR, 64, true, DRAW>;
   } else if (h->kind == 1) {
-    plain = step_kernel_split<AR>;
+    plain = step_kernel_split<AR, false, DRAW>;
   } else {
     threads = 64;
   }
   const dim3 grid(grid_for(h->n, envs));
   unsigned long long* sp = probed ? satrl_span::take(satrl_span::kEnvStep, (int64_t)grid.x * 4) : nullptr;
   satrl_span::launch_span(probed, plain, sp, grid, dim3(threads), stream, h->prm, h->n, h->f64, h->i32, io);
+}
+
+// only an autoreset step resets, so only it has DRAW instantiations
+template <bool AR>
+void launch_step(satenv_env* h, const StepIO& io, void* stream) {
+  if (AR && h->draw) launch_step_draw<AR, AR>(h, io, stream);
+  else launch_step_draw<AR, false>(h, io, stream);
 }
 
 }  // namespace
@@ -773,6 +791,11 @@ int satenv_create(satenv_env** out, int64_t num_envs, const satenv_params* p, in
   if (e == hipSuccess) e = hipMalloc(&h->i32, sizeof(int32_t) * kI32Planes * num_envs);
   if (e == hipSuccess) e = hipMalloc(&h->err, sizeof(int32_t));
   if (e == hipSuccess) e = hipMemset(h->err, 0, sizeof(int32_t));
+  ResetDist rd{};
+  satenv_default_reset_dist(&h->dist);
+  reset_dist_pack(h->dist, rd);
+  if (e == hipSuccess) e = hipMalloc(&h->rd, sizeof(ResetDist));
+  if (e == hipSuccess) e = hipMemcpy(h->rd, &rd, sizeof(ResetDist), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     satenv_destroy(h);
     return fail(SATENV_ERR_HIP, std::string("satenv_create: ") + hipGetErrorString(e));
@@ -794,6 +817,7 @@ int satenv_destroy(satenv_env* h) {
   if (h->f64) (void)hipFree(h->f64);
   if (h->i32) (void)hipFree(h->i32);
   if (h->err) (void)hipFree(h->err);
+  if (h->rd) (void)hipFree(h->rd);
   delete h;
   return SATENV_OK;
 }
@@ -816,8 +840,8 @@ int satenv_reset(satenv_env* h, int32_t flag, const uint8_t* env_mask, float* ob
   if (!h) return fail(SATENV_ERR_ARG, "satenv_reset: null handle");
   if (flag < 0 || flag > 2) return fail(SATENV_ERR_ARG, "satenv_reset: Flag must be 0, 1 or 2");
   h->prm.flag = flag;
-  hipLaunchKernelGGL(reset_kernel, dim3(grid_for(h->n, 256)), dim3(256), 0, (hipStream_t)stream, h->prm, h->n,
-                     h->f64, h->i32, flag, env_mask, obs_out, obs64_out);
+  hipLaunchKernelGGL(reset_kernel, dim3(grid_for(h->n, 256)), dim3(256), 0, (hipStream_t)stream, h->prm, h->rd,
+                     h->n, h->f64, h->i32, flag, env_mask, obs_out, obs64_out);
   HIP_TRY(hipGetLastError());
   return SATENV_OK;
 }
@@ -825,7 +849,7 @@ int satenv_reset(satenv_env* h, int32_t flag, const uint8_t* env_mask, float* ob
 int satenv_step(satenv_env* h, const float* pa, const float* ea, const int32_t* episode_count, float* obs_out,
                 double* obs64_out, double* reward_out, uint8_t* done_out, void* stream) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_step: null argument");
-  StepIO io{pa, ea, episode_count, obs_out, obs64_out, reward_out, nullptr, done_out, nullptr, h->err};
+  StepIO io{pa, ea, episode_count, obs_out, obs64_out, reward_out, nullptr, done_out, nullptr, h->err, h->rd};
   launch_step<false>(h, io, stream);
   HIP_TRY(hipGetLastError());
   return SATENV_OK;
@@ -834,7 +858,7 @@ int satenv_step(satenv_env* h, const float* pa, const float* ea, const int32_t* 
 int satenv_step_autoreset(satenv_env* h, const float* pa, const float* ea, float* obs_out, float* reward_out,
                           uint8_t* done_out, double* stats_out, void* stream) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_step_autoreset: null argument");
-  StepIO io{pa, ea, nullptr, obs_out, nullptr, nullptr, reward_out, done_out, stats_out, h->err};
+  StepIO io{pa, ea, nullptr, obs_out, nullptr, nullptr, reward_out, done_out, stats_out, h->err, h->rd};
   launch_step<true>(h, io, stream);
   HIP_TRY(hipGetLastError());
   return SATENV_OK;
@@ -859,6 +883,50 @@ int satenv_set_state(satenv_env* h, const double* f64_planes, const int32_t* i32
   if (i32_planes)
     HIP_TRY(hipMemcpyAsync(h->i32, i32_planes, sizeof(int32_t) * SATENV_I32_PLANES * h->n,
                            hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return SATENV_OK;
+}
+
+int satenv_default_reset_dist(satenv_reset_dist* d) {
+  if (!d) return fail(SATENV_ERR_ARG, "satenv_default_reset_dist: null");
+  std::memset(d, 0, sizeof(*d));
+  double k[12];
+  reset_kin(satenv_params{}, k);
+  std::memcpy(d->lo, k, sizeof(k));
+  std::memcpy(d->hi, k, sizeof(k));
+  return SATENV_OK;
+}
+
+int satenv_set_reset_dist(satenv_env* h, const satenv_reset_dist* d, void* stream) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_set_reset_dist: null argument");
+  ResetDist rd;
+  if (!reset_dist_pack(*d, rd)) return fail(SATENV_ERR_ARG, "satenv_set_reset_dist: bounds must be finite, lo <= hi");
+  hipLaunchKernelGGL(set_reset_dist_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, rd, h->rd);
+  HIP_TRY(hipGetLastError());
+  h->dist = *d;
+  h->dist.enabled = d->enabled != 0;
+  h->dist.reserved = 0;
+  if (d->enabled) h->draw = true;   // from now on the DRAW step kernels, whatever the block says later
+  return SATENV_OK;
+}
+
+int satenv_get_reset_dist(const satenv_env* h, satenv_reset_dist* d) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_get_reset_dist: null argument");
+  *d = h->dist;
+  return SATENV_OK;
+}
+
+int satenv_get_episode_index(const satenv_env* h, int32_t* out, void* stream) {
+  if (!h || !out) return fail(SATENV_ERR_ARG, "satenv_get_episode_index: null argument");
+  HIP_TRY(hipMemcpyAsync(out, h->i32 + kPlaneEp * h->n, sizeof(int32_t) * h->n, hipMemcpyDeviceToDevice,
+                         (hipStream_t)stream));
+  return SATENV_OK;
+}
+
+int satenv_set_episode_index(satenv_env* h, const int32_t* in, void* stream) {
+  if (!h) return fail(SATENV_ERR_ARG, "satenv_set_episode_index: null handle");
+  int32_t* dst = h->i32 + kPlaneEp * h->n;
+  if (in) HIP_TRY(hipMemcpyAsync(dst, in, sizeof(int32_t) * h->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  else HIP_TRY(hipMemsetAsync(dst, 0, sizeof(int32_t) * h->n, (hipStream_t)stream));
   return SATENV_OK;
 }
 

@@ -5,20 +5,54 @@
 //
 // Per-handle state layout (num_envs = N):
 //   f64 planes [16][N]  Pp0..2 Pv0..2 Ep0..2 Ev0..2 fuel_c fuel_t dis ep_return
-//   i32 planes [3][N]   dangerous_zone, episode_count, bits
+//   i32 planes [4][N]   dangerous_zone, episode_count, bits, episode index
+// (the last f64 and the last i32 plane are internal: get/set_state copy the
+// public SATENV_F64_PLANES / SATENV_I32_PLANES)
 #pragma once
+#include <cmath>
+
+#include "philox_core.h"
 #include "satenv_device.h"
 
 namespace satenv {
 
 constexpr int kF64Planes = 16;   // 15 public + per-env episode return
-constexpr int kI32Planes = 3;
+constexpr int kI32Planes = 4;   // 3 public + per-env episode index
 constexpr int kPlaneRet = 15;
-constexpr int kPlaneDz = 0, kPlaneCount = 1, kPlaneBits = 2;
+constexpr int kPlaneDz = 0, kPlaneCount = 1, kPlaneBits = 2, kPlaneEp = 3;
+constexpr uint32_t kResetStream = 2;   // philox_key stream of the reset draw (0 / 1: the agents' action noise)
 
 struct alignas(8) F32x2 { float x, y; };
 
 inline bool params_ok(const Params& p) { return p.propagator >= 0 && p.propagator <= 2 && p.rk4_substeps >= 1; }
+
+// The handle's reset distribution as the kernels read it (satenv_reset_dist,
+// include/satenv.h): a uniform box over the 12 kinematic scalars, span = hi -
+// lo rounded once on the host.  It lives in a small block owned by the handle
+// and is read only where an env resets.
+struct ResetDist {
+  double lo[12], span[12];
+  uint32_t k0, k1;        // philox_key(seed, kResetStream)
+  int64_t env_offset;     // global env id of env 0
+  int32_t enabled;
+  int32_t reserved;
+};
+
+// satenv_reset_dist -> ResetDist; false where a bound is not finite, lo > hi or hi - lo overflows
+inline bool reset_dist_pack(const satenv_reset_dist& in, ResetDist& out) {
+  for (int c = 0; c < 12; ++c) {
+    const double span = in.hi[c] - in.lo[c];
+    if (!std::isfinite(in.lo[c]) || !std::isfinite(in.hi[c]) || !(in.lo[c] <= in.hi[c]) || !std::isfinite(span))
+      return false;
+    out.lo[c] = in.lo[c];
+    out.span[c] = span;
+  }
+  philox_key(in.seed, kResetStream, out.k0, out.k1);
+  out.env_offset = in.env_offset;
+  out.enabled = in.enabled != 0;
+  out.reserved = 0;
+  return true;
+}
 
 struct StepIO {
   const float* pa;
@@ -31,6 +65,7 @@ struct StepIO {
   uint8_t* done;
   double* stats;
   int32_t* err;
+  const ResetDist* rd;        // the handle's reset distribution (never null)
 };
 
 // one env's share of a step's statistics (step_autoreset's stats_out): episode
@@ -68,6 +103,61 @@ SATENV_HD void reset_kin(const Params& /*p*/, double (&k)[12]) {
   k[6] = 18000.0;
 }
 
+// A field of the handle's ResetDist block.  The block is uniform and no launch
+// that reads it writes it (the setter is a launch of its own), so the kernels
+// read it through the constant address space: scalar loads into SGPRs, issued
+// only where an env resets.
+template <class T>
+SATENV_HD T rd_load(const T* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return *(const __attribute__((address_space(4))) T*)p;
+#else
+  return *p;
+#endif
+}
+
+// The randomised reset state of env i's episode `ep`:
+// component c is lo[c] + span[c] * u with u = (w[c] + 0.5) * 2^-32 strictly
+// inside (0, 1) and w the 12 words of three Philox4x32-10 blocks, counter
+// (global env id, ep, block), key (seed, stream 2).  Integer rounds, an exact
+// u and two f64 roundings (no contraction): the same bits on both targets.
+// No rejection: a start inside d_capture is captured on its first step.
+SATENV_HD void reset_draw(const ResetDist* d, int64_t i, uint32_t ep, double (&k)[12]) {
+  const uint64_t gid = (uint64_t)rd_load(&d->env_offset) + (uint64_t)i;
+  const uint32_t k0 = rd_load(&d->k0), k1 = rd_load(&d->k1);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    uint32_t w[4] = {(uint32_t)gid, (uint32_t)(gid >> 32), ep, (uint32_t)j};
+    philox4x32_10(w, k0, k1);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const double u = ((double)w[m] + 0.5) * 0x1p-32;
+      k[4 * j + m] = rd_load(&d->lo[4 * j + m]) + rd_load(&d->span[4 * j + m]) * u;
+    }
+  }
+}
+
+// One reset of env i (the masked reset and the autoreset): the kinematics it
+// starts from and its vel_int bit -- the reference's int64 constants (vel_int
+// 1) or, with the distribution enabled, the draw of this episode index (float
+// velocities, vel_int 0: no first-step truncation).  Every reset advances
+// the env's episode index.  kDraw = false: the instantiation of handles that
+// never enabled a distribution, without the draw's code (as kRk45 below).
+template <bool kDraw>
+SATENV_HD int reset_state(const Params& prm, const ResetDist* rd, int64_t n, int32_t* i32, int64_t i,
+                          double (&k)[12]) {
+  const int32_t ep = i32[kPlaneEp * n + i];
+  i32[kPlaneEp * n + i] = ep + 1;
+  if constexpr (kDraw) {
+    if (rd_load(&rd->enabled)) {
+      reset_draw(rd, i, (uint32_t)ep, k);
+      return 0;
+    }
+  }
+  reset_kin(prm, k);
+  return 1;
+}
+
 // env i as the constructor leaves it (environment.py:26-44)
 SATENV_HD void init_env(const Params& p, int64_t n, double* f64, int32_t* i32, int64_t i) {
 #pragma unroll
@@ -79,18 +169,19 @@ SATENV_HD void init_env(const Params& p, int64_t n, double* f64, int32_t* i32, i
   i32[kPlaneDz * n + i] = 0;                                                // :41
   i32[kPlaneCount * n + i] = 0;
   i32[kPlaneBits * n + i] = make_bits(p.fuel_c0_mode, p.fuel_t0_mode, 1, p.flag);
+  i32[kPlaneEp * n + i] = 0;
 }
 
 // reset(Flag) of env i where the mask selects it (environment.py:66-79), and its obs either way
-SATENV_HD void reset_env(const Params& prm, int64_t n, double* f64, int32_t* i32, int32_t flag, const uint8_t* mask,
-                         float* obs, double* obs64, int64_t i) {
+SATENV_HD void reset_env(const Params& prm, const ResetDist* rd, int64_t n, double* f64, int32_t* i32, int32_t flag,
+                         const uint8_t* mask, float* obs, double* obs64, int64_t i) {
   double k[12];
   if (mask == nullptr || mask[i] != 0) {
-    reset_kin(prm, k);
+    const int vi = reset_state<true>(prm, rd, n, i32, i, k);
 #pragma unroll
     for (int c = 0; c < 12; ++c) f64[c * n + i] = k[c];
     const int b = i32[kPlaneBits * n + i];
-    i32[kPlaneBits * n + i] = make_bits(fc_mode(b), ft_mode(b), 1, flag);
+    i32[kPlaneBits * n + i] = make_bits(fc_mode(b), ft_mode(b), vi, flag);
     i32[kPlaneCount * n + i] = 0;
     f64[kPlaneRet * n + i] = 0.0;
   } else {
@@ -260,6 +351,7 @@ SATENV_HD void step_reward(const Params& prm, Lane& L, int cnt) {
   step_reward_terms(prm, L, cnt, t);
 }
 
+template <bool kDraw = false>
 SATENV_HD void step_end(const Params& prm, int64_t n, double* __restrict__ f64,
                                          int32_t* __restrict__ i32, const StepIO& io, int64_t i, bool autoreset,
                                          Lane& L, StepStats& s) {
@@ -273,8 +365,7 @@ SATENV_HD void step_end(const Params& prm, int64_t n, double* __restrict__ f64,
     s.fin = 1.0;
     s.fin_ret = ret;
     ret = 0.0;
-    reset_kin(prm, L.k);
-    vi_out = 1;
+    vi_out = reset_state<kDraw>(prm, io.rd, n, i32, i, L.k);
     L.count = 0;
   }
   write_obs(io.obs, io.obs64, i, L.k);
@@ -292,7 +383,7 @@ SATENV_HD void step_end(const Params& prm, int64_t n, double* __restrict__ f64,
 // The whole step of env i in one lane (the count's four solves one after
 // another): the one-lane kernel and the host build.  Returns the error code
 // to record, 0 if none; the caller owns the (first-wins) error sink.
-template <bool kRk45>
+template <bool kRk45, bool kDraw>
 SATENV_HD int step_lane(const Params& prm, int64_t n, double* __restrict__ f64, int32_t* __restrict__ i32,
                         const StepIO& io, int64_t i, bool autoreset, StepStats& s) {
   Lane L;
@@ -304,7 +395,7 @@ SATENV_HD int step_lane(const Params& prm, int64_t n, double* __restrict__ f64, 
     if (err == 0) err = rc;
     step_reward(prm, L, cnt);
   }
-  step_end(prm, n, f64, i32, io, i, autoreset, L, s);
+  step_end<kDraw>(prm, n, f64, i32, io, i, autoreset, L, s);
   return err;
 }
 

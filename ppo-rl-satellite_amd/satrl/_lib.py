@@ -39,6 +39,12 @@ class SatenvParams(C.Structure):
                 ("cw_omega", C.c_double), ("propagator", C.c_int32), ("rk4_substeps", C.c_int32)]
 
 
+class SatenvResetDist(C.Structure):
+    """Mirror of ``satenv_reset_dist`` (include/satenv.h)."""
+    _fields_ = [("lo", C.c_double * 12), ("hi", C.c_double * 12), ("seed", C.c_uint64), ("env_offset", C.c_int64),
+                ("enabled", C.c_int32), ("reserved", C.c_int32)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -86,6 +92,16 @@ _SIGS = {
     "satenv_surrogate_set_scalers": ([_vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "satenv_ellipse_fit": ([_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "satenv_rd_orbits": ([_vp, _vp, _vp, _vp], C.c_int),
+    "satenv_default_reset_dist": ([C.POINTER(SatenvResetDist)], C.c_int),
+    "satenv_set_reset_dist": ([_vp, C.POINTER(SatenvResetDist), _vp], C.c_int),
+    "satenv_get_reset_dist": ([_vp, C.POINTER(SatenvResetDist)], C.c_int),
+    "satenv_get_episode_index": ([_vp, _vp, _vp], C.c_int),
+    "satenv_set_episode_index": ([_vp, _vp, _vp], C.c_int),
+    "satenv_cpu_default_reset_dist": ([C.POINTER(SatenvResetDist)], C.c_int),
+    "satenv_cpu_set_reset_dist": ([_vp, C.POINTER(SatenvResetDist), _vp], C.c_int),
+    "satenv_cpu_get_reset_dist": ([_vp, C.POINTER(SatenvResetDist)], C.c_int),
+    "satenv_cpu_get_episode_index": ([_vp, _vp, _vp], C.c_int),
+    "satenv_cpu_set_episode_index": ([_vp, _vp, _vp], C.c_int),
     "satenv_cpu_last_error": ([], C.c_char_p),
     "satenv_cpu_create": ([C.POINTER(_vp), _i64, C.POINTER(SatenvParams), C.c_int], C.c_int),
     "satenv_cpu_destroy": ([_vp], C.c_int),

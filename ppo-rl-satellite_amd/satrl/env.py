@@ -66,6 +66,32 @@ def rk4_j2(rv, h, steps, out=None):
     return out
 
 
+def reset_constants() -> np.ndarray:
+    """The 12 kinematic scalars of the reference's reset (environment.py:67-71)."""
+    d = _lib.SatenvResetDist()
+    check(_lib.lib().satenv_default_reset_dist(C.byref(d)), "satenv_default_reset_dist")
+    return np.array(d.lo[:])
+
+
+def reset_box(spread):
+    """args_param.reset_spread -> (lo, hi) f64 [12], or None for None: a
+    12-sequence gives half-widths around the reset's constants, a dict
+    {"lo": ..., "hi": ...} the box itself."""
+    if spread is None:
+        return None
+    if isinstance(spread, dict):
+        lo, hi = (np.asarray(spread[k], dtype=np.float64).ravel() for k in ("lo", "hi"))
+    else:
+        half = np.asarray(spread, dtype=np.float64).ravel()
+        if half.shape != (12,) or not (half >= 0).all():
+            raise ValueError("reset_spread: 12 non-negative half-widths (Pp, Pv, Ep, Ev) or a dict of lo and hi")
+        c = reset_constants()
+        lo, hi = c - half, c + half
+    if lo.shape != (12,) or hi.shape != (12,):
+        raise ValueError("reset_spread: lo and hi are 12 scalars each")
+    return lo, hi
+
+
 def _num_mode(v) -> int:
     if isinstance(v, np.float32):
         return F32
@@ -134,6 +160,7 @@ class VecSatellites:
         self._h = h
         self.observation_space, self.action_space, self.action_space_beta = _spaces()
         self.stats = torch.zeros(4, dtype=torch.float64, device=self.device)
+        self.draws = False               # set_reset_dist was called: the handle launches the drawing step kernels
 
     def _fn(self, name):
         return getattr(_lib.lib(), self._api + name)
@@ -254,6 +281,59 @@ class VecSatellites:
         if i32_planes is not None:
             self._req(i32_planes, torch.int32, (SATENV_I32_PLANES, n), "i32_planes")
         check(self._fn("set_state")(self._h, ptr(f64_planes), ptr(i32_planes), self._sp()), self._api + "set_state")
+
+    # -- randomised episode starts (include/satenv.h satenv_reset_dist) ---------
+    def _get_dist(self):
+        d = _lib.SatenvResetDist()
+        check(self._fn("get_reset_dist")(self._h, C.byref(d)), self._api + "get_reset_dist")
+        return d
+
+    def _set_dist(self, d):
+        check(self._fn("set_reset_dist")(self._h, C.byref(d), self._sp()), self._api + "set_reset_dist")
+
+    def set_reset_dist(self, lo, hi, seed, env_offset: int = 0):
+        """From now on every reset of env i -- reset() and the autoreset inside
+        step_autoreset -- starts from a point drawn uniformly from the box
+        [lo, hi] (12 scalars: Pp, Pv, Ep, Ev), a function of (seed, env_offset
+        + i, the env's episode index) alone.  Stream-ordered: graphs captured
+        earlier see it on their next replay -- except graphs captured before
+        this handle's first set_reset_dist (`draws` still False), which hold
+        the step kernel without the draw and must be captured again.  There
+        is no rejection: a start inside d_capture is captured on its first step."""
+        d = _lib.SatenvResetDist()
+        lo, hi = (np.asarray(x, dtype=np.float64).ravel() for x in (lo, hi))
+        if lo.shape != (12,) or hi.shape != (12,):
+            raise ValueError("lo and hi are 12 scalars each: Pp[3], Pv[3], Ep[3], Ev[3]")
+        d.lo[:], d.hi[:] = lo.tolist(), hi.tolist()
+        d.seed, d.env_offset, d.enabled = int(seed) & (2 ** 64 - 1), int(env_offset), 1
+        self._set_dist(d)
+        self.draws = True
+
+    def clear_reset_dist(self):
+        """Back to the reference's fixed reset (the episode indices keep counting)."""
+        d = self._get_dist()
+        d.enabled = 0
+        self._set_dist(d)
+
+    @property
+    def reset_dist(self):
+        """None while resets are the reference's, else a dict: lo, hi (f64 [12]), seed, env_offset."""
+        d = self._get_dist()
+        if not d.enabled:
+            return None
+        return {"lo": np.array(d.lo[:]), "hi": np.array(d.hi[:]), "seed": int(d.seed), "env_offset": int(d.env_offset)}
+
+    def episode_index(self):
+        """int32 [N]: how many resets each env has had (0 at construction)."""
+        out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        check(self._fn("get_episode_index")(self._h, ptr(out), self._sp()), self._api + "get_episode_index")
+        return out
+
+    def set_episode_index(self, t=None):
+        """Set the per-env episode indices (int32 [N]; None: zeros)."""
+        if t is not None:
+            self._req(t, torch.int32, (self.num_envs,), "episode index")
+        check(self._fn("set_episode_index")(self._h, ptr(t), self._sp()), self._api + "set_episode_index")
 
     def check_errors(self) -> int:
         st = C.c_int32(0)

@@ -89,14 +89,16 @@ class EvalResult:
     env steps run.  ``streams`` (record=True): the per-step tensors
     [steps, num_envs, ...] named in STREAMS -- ``obs`` / ``obs64`` / ``reward``
     / ``done`` are step t's outputs, ``policy_input`` and the actions its
-    inputs."""
+    inputs.  ``start`` (f64 [12, num_envs]): the kinematics Pp Pv Ep Ev each
+    recorded episode began from."""
 
-    def __init__(self, rec_f64, rec_i32, steps, flag, det_mask, seed, streams=None):
+    def __init__(self, rec_f64, rec_i32, steps, flag, det_mask, seed, streams=None, start=None):
         for k, name in enumerate(REC_F64):
             setattr(self, name, rec_f64[k])
         for k, name in enumerate(REC_I32):
             setattr(self, name, rec_i32[k])
         self.steps, self.flag, self.det_mask, self.seed, self.streams = steps, flag, det_mask, seed, streams
+        self.start = start
 
     def summary(self):
         """Host statistics.  ``episodes``: finished episodes, ``unfinished``:
@@ -122,7 +124,9 @@ class EvalResult:
 class VecEvaluator:
     """Evaluation of ``trainer``'s policies on ``num_envs`` envs of its own
     (default: the trainer's N) with the trainer's env parameters.  ``seed``
-    keys the sampling agents' noise (default args.seed ^ EVAL_SEED_XOR)."""
+    keys the sampling agents' noise (default args.seed ^ EVAL_SEED_XOR) and,
+    where the trainer's env draws randomised starts, the evaluator's draws
+    from the same box."""
 
     MAX_GRAPHS = 16
 
@@ -220,12 +224,21 @@ class VecEvaluator:
                 self._step(0, det_mask, seed, cap)
                 torch.cuda.synchronize()
                 self._warm = True
+            # the trainer's reset box as it is now, under the evaluation seed and from episode index
+            # 0: the same scenarios on every call
+            box = tr.env.reset_dist
+            if box is None:
+                env.clear_reset_dist()
+            else:
+                env.set_reset_dist(box["lo"], box["hi"], seed, env_offset=tr.env_offset)
+            env.set_episode_index(None)
             if states is None:
                 env.set_state(*self._state0)
                 env.reset(flag, obs_out=self.obs_raw)
             else:
                 env.set_state(*states)           # the caller's scenarios: no reset, the obs of the state as it is
                 env.reset(flag, mask=self._no_mask, obs_out=self.obs_raw)
+            start = env.get_state()[0][:12].clone()
             episode_record_reset(self.rec_f64, self.rec_i32, self.alive)
             rec = None
             out = self._stream_buffers(max_steps) if record else None
@@ -251,4 +264,4 @@ class VecEvaluator:
                     break
             if record:
                 out = {k: v[:t] for k, v in out.items()}
-            return EvalResult(self.rec_f64.clone(), self.rec_i32.clone(), t, flag, det_mask, seed, out)
+            return EvalResult(self.rec_f64.clone(), self.rec_i32.clone(), t, flag, det_mask, seed, out, start)

@@ -11,7 +11,8 @@
   advantage normalisation, and the graph-captured minibatch update.
   One process per GPU; with a process group the envs are sharded by global
   env id (Philox noise keyed by it, so rollouts do not depend on sharding)
-  and gradients are averaged with RCCL.  Opt-in (obs_norm, reward_scaling):
+  and gradients are averaged with RCCL.  Opt-in (reset_spread): every episode
+  starts from a point drawn from a box, per env and episode.  Opt-in (obs_norm, reward_scaling):
   running observation normalisation and reward scaling, satrl/norm.py.
   ``VecTrainer.evaluate`` measures the current policies on a fresh env handle
   without touching any training state, satrl/evaluate.py.  Opt-in
@@ -45,7 +46,7 @@ class args_param:  # noqa: N801
                  num_envs=1, horizon=None, seed=0, rollout_graph_chunk=64, update_graph_group=64, device=None,
                  surrogate=False, dp_minibatch="global", minibatch_sampler=None, allreduce="rccl",
                  obs_norm=False, reward_scaling=False, obs_clip=10.0, obs_norm_calib_steps=64,
-                 diagnostics=False, diagnostics_rows=None, target_kl=None):
+                 diagnostics=False, diagnostics_rows=None, target_kl=None, reset_spread=None, reset_seed=None):
         self.max_train_steps = max_train_steps
         self.evaluate_freq = evaluate_freq
         self.save_freq = save_freq
@@ -125,6 +126,14 @@ class args_param:  # noqa: N801
         self.diagnostics = diagnostics
         self.diagnostics_rows = diagnostics_rows
         self.target_kl = target_kl
+        # randomised episode starts of the vectorised engine (include/satenv.h
+        # satenv_reset_dist): None = the reference's fixed reset; 12 half-widths
+        # (Pp, Pv, Ep, Ev; metres and m/s) around the reset's constants, or
+        # {"lo": ..., "hi": ...} for the box itself.  Every reset, the in-kernel
+        # autoreset included, then draws its start from the box, keyed by
+        # (reset_seed, global env id, the env's episode index); reset_seed None = seed
+        self.reset_spread = reset_spread
+        self.reset_seed = reset_seed
         # set by the train_* functions from the env (CPPO_main.py:99-101)
         self.state_dim = 18
         self.action_dim = 3
@@ -352,6 +361,9 @@ class VecTrainer:
             self.ellipse_params = torch.zeros((self.N, 10), dtype=torch.float32, device=self.device)
         if self.obs_norm or self.reward_scaling:
             self._setup_norm(args)
+        rs = getattr(args, "reset_seed", None)
+        self.reset_seed = self.seed if rs is None else int(rs)
+        self.set_reset_spread(getattr(args, "reset_spread", None))
         self._reset_obs()
         if self.obs_norm and int(getattr(args, "obs_norm_calib_steps", 64)) > 0:
             self._calibrate_obs_norm(int(args.obs_norm_calib_steps))
@@ -388,6 +400,27 @@ class VecTrainer:
         self.obs_stats.copy_(torch.from_numpy(st))
         self.obs_pivot.copy_(torch.from_numpy(st[0].copy()))
 
+    def set_reset_spread(self, spread, seed=None):
+        """The box the env's resets draw their starts from (args_param
+        reset_spread; None: the reference's fixed reset), keyed by `seed`
+        (default: the current reset seed) and this rank's env_offset.  The
+        env reads it where it resets, so it holds from the next reset on; the
+        captured rollout graphs are replayed as they are.  (Only the first
+        box of a trainer built without one drops them: they hold the step
+        kernel without the draw, VecSatellites.set_reset_dist.)"""
+        from .env import reset_box
+        if seed is not None:
+            self.reset_seed = int(seed)
+        box = reset_box(spread)
+        self.reset_spread = spread
+        if box is None:
+            self.env.clear_reset_dist()
+            return
+        drew = self.env.draws
+        self.env.set_reset_dist(box[0], box[1], self.reset_seed, env_offset=self.env_offset)
+        if not drew:
+            self._graphs.clear()
+
     def _reset_obs(self):
         """Every env restarts; buf.obs[0] is the (normalised) reset observation."""
         if not self.obs_norm:
@@ -408,11 +441,14 @@ class VecTrainer:
     def _calibrate_obs_norm(self, steps):
         """First statistics from `steps` eager throw-away steps under the
         identity (mean 0, inv_std 1) with the reset observation's row 0 as the
-        pivot; the env state, env.stats and the step counters are restored."""
+        pivot; the env state, its episode indices (so the calibration does not
+        shift which starts the training draws), env.stats and the step
+        counters are restored."""
         piv = self.obs_raw[0].clone()
         _dist.broadcast_([piv], self.pg)
         self.obs_pivot.copy_(piv)
         f, i = self.env.get_state()
+        ep = self.env.episode_index()
         st, raw0 = self.env.stats.clone(), self.obs_raw.clone()
         for s_ in range(steps):
             self.step_base.fill_(s_)
@@ -420,6 +456,7 @@ class VecTrainer:
             self.buf.obs[0].copy_(self.buf.obs[1])
         self._obs_acc_rows += steps * self.N
         self.env.set_state(f, i)
+        self.env.set_episode_index(ep)
         self.env.stats.copy_(st)
         self.obs_raw.copy_(raw0)
         self.step_base.zero_()
@@ -590,9 +627,11 @@ class VecTrainer:
                 # eager warm-up of one step so lazy allocations happen before capture
                 # (restores the env state afterwards)
                 f, i = self.env.get_state()
+                ep = self.env.episode_index()
                 st = self.env.stats.clone()
                 self._policy_step(0)
                 self.env.set_state(f, i)
+                self.env.set_episode_index(ep)
                 self.env.stats.copy_(st)
                 if self.obs_norm:                # the warm-up row is not part of the iteration's sums
                     self.obs_acc.zero_()
@@ -725,7 +764,10 @@ class VecTrainer:
         `seed` (default args.seed ^ evaluate.EVAL_SEED_XOR), agent id, global
         env id and a step counter that starts at 0, so equal calls give equal
         bits.  states=(f64_planes, i32_planes): start from these env states
-        (VecSatellites.set_state) instead of reset(Flag).  record=True keeps
+        (VecSatellites.set_state) instead of reset(Flag).  With reset_spread the
+        evaluator's env draws its starts from the same box under the
+        evaluation seed, from episode index 0 on every call: a fixed test set
+        of num_envs distinct scenarios (EvalResult.start).  record=True keeps
         the per-step streams (EvalResult.streams).  No state of the trainer
         changes.  Under data parallelism each rank evaluates its own envs;
         results are not reduced across ranks."""
