@@ -176,6 +176,24 @@ int satrl_ppo_dw2_kx_w1(int H, int mb, int net, int S, const void* H1x, const vo
  * (1; 0 = none), and on an error re-arms the exchange state (the update
  * that saw it must be discarded).                                          */
 int satrl_ppo_rowpass_error(int* err, double timeout_s, void* stream);
+/* Development switch (A/B timing, and the tests' bitwise oracle): how the
+ * phases of the 32-row 16-wave k-packed rowpass kernel (satrl_ppo_rowpass_kx
+ * above 1024 rows) wait for each other inside a workgroup.  0: workgroup
+ * barriers; 1: per-chunk LDS hand-offs (the same kernel source, every output
+ * bit the same; a hand-off wait that runs out -- never, unless the kernel
+ * is wrong -- sets the error word satrl_ppo_rowpass_error reports and the
+ * kernel still ends).  Process-wide, read at launch (a captured graph keeps
+ * the form it was captured with).  Returns the previous mode; mode -1 only
+ * queries; anything else -1.                                               */
+int satrl_ppo_rowpass_sync(int mode);
+/* satrl_ppo_rowpass_kx on that 32-row kernel whatever the minibatch size (the
+ * kernel tests' entry: one block, ragged blocks, either block placement), in
+ * the form satrl_ppo_rowpass_sync selects: ceil(mb / 32) slabs of ptail / pw1
+ * (never more than satrl_ppo_sizes gives), the planes as satrl_ppo_rowpass_kx,
+ * and the actor's per-row ratio in ratio [mb] (nullable).                  */
+int satrl_ppo_rowpass_kx32(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
+                           const void* W2X, float epsilon, float ent_coef, float max_action, void* H1x, void* dZ2x,
+                           int64_t kx_elems, float* ptail, float* pw1, float* ratio, void* stream);
 /* Fault injection for tests: sets (row block, net) group `group`'s exchange
  * counter to `value` (synchronising the stream).  A value that breaks the
  * counter's invariant (a multiple of 8 at every launch's start, e.g. 5)

@@ -12,6 +12,7 @@
 // Every reduction has a fixed order, so a step is bitwise reproducible.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -423,9 +424,15 @@ __device__ __forceinline__ void a3_chunk(const unsigned short* __restrict__ ap, 
 // there, kBPD chunks ahead, its first chunks optionally issued early (pre)
 constexpr int kBPD3 = 2;          // B chunks in flight ahead of the MFMAs
 constexpr int kADB3 = 1;          // A chunk buffers (2: the next chunk's LDS reads before this one's MFMAs: no faster)
-template <int K, int LDP, int PS, int LDB, int RT, int CT, bool PRE = false>
+// wait(c): called before the A operand reads of chunk c (the rowpass's
+// hand-off form waits there for the waves that wrote the chunk's columns,
+// RpHandoff below; NoChunkWait: the caller's barrier covers all of A)
+struct NoChunkWait {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+template <int K, int LDP, int PS, int LDB, int RT, int CT, bool PRE = false, class Wait = NoChunkWait>
 __device__ __forceinline__ void mfma_rows3(const unsigned short* __restrict__ A, const float* __restrict__ B, int n0,
-                                           f4 (&acc)[RT][CT], const WPre<CT>* pre = nullptr) {
+                                           f4 (&acc)[RT][CT], const WPre<CT>* pre = nullptr, Wait wait = Wait()) {
   constexpr int NC = K / 32;
   constexpr int BPD = kBPD3 < NC ? kBPD3 : NC, NB = BPD + 1;
   static_assert(!PRE || BPD >= kBPD, "early-issued chunks fit the ring");
@@ -445,13 +452,20 @@ __device__ __forceinline__ void mfma_rows3(const unsigned short* __restrict__ A,
 #pragma unroll
     for (int c = 0; c < BPD; ++c) b_chunk<CT>(bp + 32 * c, LDB, bb[c]);
   }
-  if constexpr (kADB3 == 2) a3_chunk<LDP, PS, RT>(ap, aa[0]);
+  if constexpr (kADB3 == 2) {
+    wait(0);
+    a3_chunk<LDP, PS, RT>(ap, aa[0]);
+  }
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     if (c + BPD < NC) b_chunk<CT>(bp + 32 * (c + BPD), LDB, bb[(c + BPD) % NB]);
     if constexpr (kADB3 == 2) {
-      if (c + 1 < NC) a3_chunk<LDP, PS, RT>(ap + 32 * (c + 1), aa[(c + 1) % 2]);
+      if (c + 1 < NC) {
+        wait(c + 1);
+        a3_chunk<LDP, PS, RT>(ap + 32 * (c + 1), aa[(c + 1) % 2]);
+      }
     } else {
+      wait(c);
       a3_chunk<LDP, PS, RT>(ap + 32 * c, aa[0]);
     }
     mfma3_regs<RT, CT>(aa[kADB3 == 2 ? c % 2 : 0], bb[c % NB], acc);
@@ -595,6 +609,142 @@ __device__ __forceinline__ void store_rows(float* __restrict__ out, int ld, int 
 // measured no faster, EXPERIMENTS.md round 3).
 __device__ __forceinline__ void rp_barrier() { __syncthreads(); }
 
+// the rowpass error word (word 0): a column-split exchange (rowpass_cs_kernel)
+// or an LDS hand-off (RpHandoff) that ran out of its wait;
+// satrl_ppo_rowpass_error reports and clears it
+__device__ __attribute__((aligned(128))) unsigned g_cs_err[32];
+
+// ---------------------------------------------------------------------------
+// How the phases of a rowpass workgroup wait for each other: a template
+// parameter (Sync) of the shared phase functions, two forms.
+//
+// RpBarrier: a workgroup barrier (rp_barrier) between the phases.  Every MLP
+// kernel but the one below, and that kernel's own other instantiation.
+//
+// RpHandoff (the 32-row 16-wave H 256 k-packed rowpass): the barriers after
+// the gather's are replaced by the dependencies the data really has, as LDS
+// words (RpFlags) that a producer sets once its own LDS writes have landed
+// (s_waitcnt lgkmcnt(0), then one lane's LDS atomic) and a consumer polls
+// (one lane's ds_read, s_sleep between reads):
+//   h1   bit w: wave w's columns of the H1 planes (phase A).  Phase B's
+//        chunk c reads H1 columns 32c .. 32c+31 only: it waits for bits 2c
+//        and 2c+1, so the oldest waves of a SIMD start B while its youngest
+//        are still in fc1.
+//   out  count: waves whose output-layer partials are in osum (and, from the
+//        last wave, the head's constants).  Only wave 0 (the loss head)
+//        waits for all NW.
+//   dz3  wave 0's dz3s are written (the loss head is done): every other
+//        wave waits for it before its tail.
+//   dz   bit w: wave w's columns of the dZ2 planes (the tail); phase D's
+//        chunk c waits for bits 2c and 2c+1.
+// One word holds the 16 bits of h1 (of dz), so a wave that finds every bit
+// set on its first read reads no flag again.  Thread 0 zeroes the words before
+// the gather's barrier, which stays; each is used once per launch, so there
+// are no epochs and nothing carries over from launch to launch.
+// Dependency order, a DAG over (phase, wave) after the gather's barrier:
+//   A(w) -> B(v) chunk w/2, every v;  B(w) -> out(w);  out(all) -> head (wave 0);
+//   head -> tail(w), every w;  tail(w) -> D(v) chunk w/2, every v;  D(w) -> E(w).
+// A producer step (A, out, head, tail) waits only for steps to its left, never
+// for a consumer, and all NW waves of a workgroup are resident together, so
+// every wait ends.  No global-memory hand-off, no wait on another workgroup,
+// no wait on vmcnt: the plane stores and early weight chunks stay in flight.
+// Every poll is bounded (kRpPollMax sleeps, tens of ms): on running out the
+// wave sets the rowpass error word and goes on, so a wrong flag ends as a
+// reported error (satrl_ppo_rowpass_error), never as a hang.
+// The arithmetic, the chunk and MFMA order and every operand are the barrier
+// form's: every output bit is the same.
+// ---------------------------------------------------------------------------
+struct RpFlags {
+  unsigned h1, dz, out, dz3;
+};
+__device__ __forceinline__ unsigned rp_wave() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+constexpr unsigned kRpPollMax = 1u << 19;
+
+// this wave's LDS writes have landed; then lane 0's LDS atomic (OR: a bit, else add 1)
+template <bool OR>
+__device__ __forceinline__ void rp_publish(unsigned* word, unsigned v) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  if ((threadIdx.x & 63) == 0) {
+    if constexpr (OR) __hip_atomic_fetch_or(word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else __hip_atomic_fetch_add(word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+}
+__device__ __forceinline__ unsigned rp_read(const unsigned* word) {
+  unsigned v = 0;
+  if ((threadIdx.x & 63) == 0) v = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  return __builtin_amdgcn_readfirstlane(v);
+}
+// waits until (word & mask) == mask (word >= mask: a count, with GE); returns the word
+template <bool GE = false>
+__device__ __forceinline__ unsigned rp_wait(const unsigned* word, unsigned mask) {
+  unsigned v = rp_read(word);
+#pragma nounroll
+  for (unsigned it = 0; GE ? v < mask : (v & mask) != mask; ++it) {
+    if (it == kRpPollMax) {
+      if ((threadIdx.x & 63) == 0) __hip_atomic_store(&g_cs_err[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      break;
+    }
+    __builtin_amdgcn_s_sleep(1);
+    v = rp_read(word);
+  }
+  asm volatile("" ::: "memory");                                   // the payload's LDS reads stay behind the poll
+  return v;
+}
+
+// (the stamp numbers of the two forms agree: 1, 4, 5 = the wave passed the
+// wait -- in the hand-off form its first chunk's)
+struct RpBarrier {
+  static constexpr bool kHandoff = false;
+  __device__ __forceinline__ void init() {}
+  __device__ __forceinline__ void after_gather() {}
+  __device__ __forceinline__ void h1_written() { rp_barrier(); PHASE_PROBE(1); }
+  __device__ __forceinline__ void out_written() { rp_barrier(); }
+  __device__ __forceinline__ void wait_out() {}
+  __device__ __forceinline__ void head_done() { rp_barrier(); PHASE_PROBE(4); }
+  __device__ __forceinline__ void dz_written() { rp_barrier(); PHASE_PROBE(5); }
+  __device__ __forceinline__ NoChunkWait wait_h1() { return NoChunkWait(); }
+  __device__ __forceinline__ NoChunkWait wait_dz() { return NoChunkWait(); }
+};
+template <int NW, class Head>
+struct RpHandoff {
+  static constexpr bool kHandoff = true;
+  static_assert(NW == 16, "a 32-column chunk is two waves' tiles; 16 bits per word");
+  RpFlags& f;
+  Head head;                                                        // the head's constants (head_consts)
+  __device__ __forceinline__ void init() {
+    if (threadIdx.x == 0) f = RpFlags{0u, 0u, 0u, 0u};
+  }
+  __device__ __forceinline__ void after_gather() { head(); }
+  __device__ __forceinline__ void h1_written() { rp_publish<true>(&f.h1, 1u << rp_wave()); }
+  __device__ __forceinline__ void out_written() { rp_publish<false>(&f.out, 1u); }
+  __device__ __forceinline__ void wait_out() {
+    if (threadIdx.x < 64) rp_wait<true>(&f.out, (unsigned)NW);
+  }
+  __device__ __forceinline__ void head_done() {
+    if (threadIdx.x < 64) rp_publish<false>(&f.dz3, 1u);
+    else rp_wait<true>(&f.dz3, 1u);
+    PHASE_PROBE(4);
+  }
+  __device__ __forceinline__ void dz_written() { rp_publish<true>(&f.dz, 1u << rp_wave()); }
+  // before the A operand reads of chunk c: the two waves that wrote its columns
+  template <int STAMP>
+  struct ChunkWait {
+    const unsigned* word;
+    unsigned seen;
+    __device__ __forceinline__ void operator()(int c) {
+      const unsigned m = 3u << (2 * c);
+      if ((seen & m) != m) seen = rp_wait(word, m);
+      if (c == 0) PHASE_PROBE(STAMP);
+    }
+  };
+  __device__ __forceinline__ ChunkWait<1> wait_h1() { return ChunkWait<1>{&f.h1, 0u}; }
+  __device__ __forceinline__ ChunkWait<5> wait_dz() { return ChunkWait<5>{&f.dz, 0u}; }
+};
+template <int NW, class Head>
+__device__ __forceinline__ RpHandoff<NW, Head> rp_handoff(RpFlags& f, Head head) {
+  return RpHandoff<NW, Head>{f, head};
+}
+
 // ---------------------------------------------------------------------------
 // The phases that rowpass_kernel (its forward part through mlp_forward) and
 // the column-split rowpass_cs_kernel both run, written once: the column-split
@@ -642,8 +792,9 @@ __device__ __forceinline__ void head_consts(float& hls_d, float& hb3_d, float (&
 
 // rows r0 .. r0 + R of the minibatch (staged: src rows; else src[idx[row]])
 // -> S (the state) and ax (a, logp_old, adv, v_target), thread t0 of nt; the
-// head's constants on the way
-template <int R, int NT, int LDS_S>
+// head's constants on the way (HEADC; the hand-off rowpass computes them
+// after the gather's barrier instead, RpHandoff::after_gather)
+template <int R, int NT, bool HEADC = true, int LDS_S>
 __device__ __forceinline__ void gather_rows(int mb, const float* __restrict__ src, const int64_t* __restrict__ idx,
                                             int r0, int t0, int nt, float (&S)[R][LDS_S], float (&ax)[R][8],
                                             float& hls_d, float& hb3_d, float (&hcs)[3][3], float (&hb3s)[4]) {
@@ -656,7 +807,7 @@ __device__ __forceinline__ void gather_rows(int mb, const float* __restrict__ sr
     const int r = (t0 >> 3) & (R - 1), c4 = t0 & 7, row = r0 + r;
     const bool in = t0 < R * 8;
     float4 v = reinterpret_cast<const float4*>(src)[(int64_t)(row < mb ? row : mb - 1) * 8 + c4];
-    head_consts<NT>(hls_d, hb3_d, hcs, hb3s);
+    if constexpr (HEADC) head_consts<NT>(hls_d, hb3_d, hcs, hb3s);
     if (row >= mb) v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (in) {
       const float e4[4] = {v.x, v.y, v.z, v.w};
@@ -673,7 +824,7 @@ __device__ __forceinline__ void gather_rows(int mb, const float* __restrict__ sr
       const float v = row < mb ? src[idx[row] * 32 + c] : 0.0f;
       if (c < 18) S[r][c] = v; else ax[r][c - 18] = v;
     }
-    head_consts<NT>(hls_d, hb3_d, hcs, hb3s);
+    if constexpr (HEADC) head_consts<NT>(hls_d, hb3_d, hcs, hb3s);
   }
 }
 
@@ -992,17 +1143,20 @@ struct MlpSmem {
 // per-wave dot products (after a barrier).  h1out (nullable): row r of
 // tanh(fc1) goes to h1out[r * H + n].  PRIO: the caller raised the wave's
 // issue priority (s_setprio) for its weight loads; it drops back once phase
-// B's are all out (the policy kernel, see there).
-template <int H, int NW, int R, bool APRE, bool PRIO = false, class Gather>
+// B's are all out (the policy kernel, see there).  sync: how the phases wait
+// for each other (RpBarrier / RpHandoff above; with RpHandoff osum is complete
+// only after sync.wait_out(), which the caller issues where it reads osum).
+template <int H, int NW, int R, bool APRE, bool PRIO = false, class Gather, class Sync = RpBarrier>
 __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* __restrict__ P,
                                             int net, int nvalid,
                                             Gather gather, float* __restrict__ h1out,
                                             f4 (&acc)[R / 16][H / 16 / NW],
                                             float (&h1)[R / 16][H / 16 / NW][4],
                                             float (&w3)[H / 16 / NW][3],
-                                            unsigned (&h1w)[R / 16][H / 16 / NW][6]) {
+                                            unsigned (&h1w)[R / 16][H / 16 / NW][6], Sync sync = Sync()) {
   constexpr int RT = R / 16, LDA = H + 4, CT = H / 16 / NW, LDS_S = 36, NT = NW * 64;
   static_assert(CT >= 1 && H % (16 * NW) == 0, "tile split");
+  static_assert(!Sync::kHandoff || kBf3<H>, "the hand-off form waits inside mfma_rows3");
   const Layout L = layout(H);
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, li = l & 15, lg = l >> 4;
   const int n0 = w * (H / NW);
@@ -1035,9 +1189,11 @@ __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* 
   }
   gather(tid, NT);
   pad_rows<NT>(sm.S, nvalid);
+  sync.init();
   PHASE_PROBE(8);
   rp_barrier();
   PHASE_PROBE(9);
+  sync.after_gather();
   // (split-bf16 fc2) phase B's first weight chunks go out now, under fc1 (an
   // LDS-only barrier below, leaving them in flight, measured no faster)
   WPre<CT> preB;
@@ -1079,13 +1235,12 @@ __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* 
     }
   if (h1out != nullptr) store_rows<R, CT>(h1out, H, n0, nvalid, h1);   // straight-line unless ragged
   PHASE_PROBE(11);
-  rp_barrier();
-  PHASE_PROBE(1);
+  sync.h1_written();                                               // (stamp 1 in there, or in B's first wait)
 
   // ---- B: Z2 = H1 W2^T -------------------------------------------------------
   if constexpr (kBf3<H>)
     mfma_rows3<H, MlpSmem<H, NW, R>::LDP, MlpSmem<H, NW, R>::PS, H, RT, CT, true>(
-        sm.h1p, P + L.W2 + (int64_t)net * H * H, n0, acc, &preB);
+        sm.h1p, P + L.W2 + (int64_t)net * H * H, n0, acc, &preB, sync.wait_h1());
   else
     mfma_rows<H, LDA, H, RT, CT, APRE>(&sm.h1s[0][0], P + L.W2 + (int64_t)net * H * H, n0, acc);
   if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
@@ -1093,11 +1248,13 @@ __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* 
 
   // ---- C (forward part): fc2 tanh, output-layer dot products -----------------
   fc2_out_partials(acc, b2v, w3, net, li, lg, sm.osum, w * CT);
-  rp_barrier();
+  sync.out_written();
   PHASE_PROBE(3);
 }
 
-template <int H, int NW, int R = kRows, bool FDW2 = false, bool KX = false, bool SPAN = false>
+// HANDOFF: the phases hand over by LDS words (RpHandoff) instead of workgroup
+// barriers: the 32-row 16-wave k-packed kernel only, bitwise the same
+template <int H, int NW, int R = kRows, bool FDW2 = false, bool KX = false, bool HANDOFF = false, bool SPAN = false>
 __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb, int net_sel,
                                                       const float* __restrict__ src, const int64_t* __restrict__ idx,
                                                       const float* __restrict__ P, const void* __restrict__ W2X,
@@ -1117,6 +1274,7 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   // u16 [2][3][kx_rows(mb)][H]) for satrl_ppo_dw2_kx, whole 32-row chunks (a
   // 16-row kernel's last block zero-fills the chunk's other half)
   static_assert(!KX || ((R == 32 || R == kRowsShort) && kBf3<H> && !FDW2), "k-packed outputs: split-bf16 width");
+  static_assert(!HANDOFF || (KX && R == 32 && NW == 16), "hand-offs: the 32-row 16-wave k-packed kernel");
   const int64_t PLX = kx_rows(mb) * H;                             // (KX) plane elements per net
   const Layout L = layout(H);
   __shared__ MlpSmem<H, NW, R> sm;
@@ -1163,8 +1321,14 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   float w3[CT][3];
   unsigned h1w[RT][CT][6];                                         // (split-bf16) the split H1 words
   auto gather = [&](int t0, int nt) {
-    gather_rows<R, NT>(mb, src, idx, r0, t0, nt, S, ax, hls_d, hb3_d, hcs, hb3s);
+    gather_rows<R, NT, !HANDOFF>(mb, src, idx, r0, t0, nt, S, ax, hls_d, hb3_d, hcs, hb3s);
   };
+  // how the phases wait for each other (RpBarrier / RpHandoff)
+  __shared__ RpFlags flags;
+  auto sync = [&] {
+    if constexpr (HANDOFF) return rp_handoff<NW>(flags, [&] { head_consts<NT>(hls_d, hb3_d, hcs, hb3s); });
+    else return RpBarrier();
+  }();
   // the fc2 operand image: the f32 W2^T
   const float* W2T = static_cast<const float*>(W2X);
   // (H = 256: the H1 store after phase B, not between fc1 and B: 8 fewer VGPRs
@@ -1175,9 +1339,10 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   if constexpr (FDW2) __builtin_amdgcn_s_setprio(3);
   mlp_forward<H, NW, R, true, FDW2>(sm, P, net, mb - r0, gather,
                                    FDW2 || KX || BF3 ? nullptr : H1g + ((int64_t)net * mb + r0) * H, acc, h1, w3,
-                                   h1w);
+                                   h1w, sync);
   // (KX) the H1 planes: wave 0, which runs the loss head next, stores its
-  // share after the head's barrier, off the head's path; the other waves now
+  // share after the head's barrier (hand-off), off the head's path; the
+  // other waves now
   unsigned short* const H1x = reinterpret_cast<unsigned short*>(H1g);
   unsigned short* const dZ2x = reinterpret_cast<unsigned short*>(dZ2g);
   if constexpr (KX) {
@@ -1190,10 +1355,10 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
 
   // ---- C: the net's loss and its gradient, dZ2 ---------------------------------
   float* tp = ptail + (int64_t)rb * L.tail;                         // tail-relative slab of this row block
+  sync.wait_out();                                                  // (hand-off: wave 0, for every wave's partials)
   loss_head<H, R, true>(mb, r0, net, inv_mb, epsilon, ent_coef, max_action, sm.osum, hcs, hb3s, ax, dz3s, tp,
                         ratio_out, true);
-  rp_barrier();
-  PHASE_PROBE(4);
+  sync.head_done();                                                 // dz3s is ready (stamp 4)
   // (wave 0's share of the H1 planes after the head's barrier: before it, the
   // barrier's vmcnt(0) waited for those stores' write latency with the other
   // 15 waves idle -- in-graph step 47.73-47.88 against 47.99-48.51 us over
@@ -1204,11 +1369,11 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   float d2v[RT][CT][4];
   unsigned d2w[RT][CT][6];                                         // (split-bf16) the split dZ2 words
   tail<H, RT, CT, LDP, PS>(acc, w3, dz3s, &dzs[0][0], dzp, d2v, d2w, tp, net, n0);
+  if constexpr (HANDOFF) sync.dz_written();                            // (before the plane stores: they drain under D)
   if constexpr (KX)
     store_kx_w<H, R, CT, R == kRowsShort>(dZ2x + net * 3 * PLX, PLX, r0, n0, d2w);
   else if constexpr (!FDW2) store_rows<R, CT>(dZ2g + ((int64_t)net * mb + r0) * H, H, n0, mb - r0, d2v);
-  rp_barrier();
-  PHASE_PROBE(5);
+  if constexpr (!HANDOFF) sync.dz_written();                           // the barrier (stamp 5; hand-off: in D's first wait)
 
   // ---- D: dH1 = dZ2 W2 -------------------------------------------------------
 #pragma unroll
@@ -1216,7 +1381,7 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
 #pragma unroll
     for (int t = 0; t < CT; ++t) acc[rt][t] = f4{0.f, 0.f, 0.f, 0.f};
   if constexpr (BF3)
-    mfma_rows3<H, LDP, PS, H, RT, CT, true>(dzp, W2T + (int64_t)net * H * H, n0, acc, &preD);
+    mfma_rows3<H, LDP, PS, H, RT, CT, true>(dzp, W2T + (int64_t)net * H * H, n0, acc, &preD, sync.wait_dz());
   else
     mfma_rows<H, LDA, H, RT, CT, true, true>(&dzs[0][0], W2T + (int64_t)net * H * H, n0, acc, &preD);
   PHASE_PROBE(6);
@@ -1302,7 +1467,6 @@ constexpr int kCsMaxMb = 1024;
 constexpr int kCsMaxGroups = 2 * (kCsMaxMb / kRowsShort);      // (row block, net) groups
 constexpr unsigned long long kCsTimeoutTicks = 50000000ull;     // 0.5 s of s_memrealtime (100 MHz)
 __device__ __attribute__((aligned(128))) unsigned g_cs_ctr[kCsMaxGroups][32];   // a 128-B line per counter
-__device__ __attribute__((aligned(128))) unsigned g_cs_err[32];
 __device__ __attribute__((aligned(128))) float g_cs_x1[kCsMaxGroups][kCsSplit][kRowsShort][3][kCsWaves];
 __device__ __attribute__((aligned(128))) unsigned short g_cs_x2[kCsMaxGroups][3][kRowsShort][256];
 
@@ -2576,9 +2740,9 @@ void launch_policy(int H, int kind, dim3 g, void* stream, A... args) {
                 args...);
 }
 // the two instantiations of a rowpass_kernel, {probed, plain}
-template <int H, int NW, int R, bool FDW2, bool KX>
+template <int H, int NW, int R, bool FDW2, bool KX, bool HANDOFF = false>
 auto rowpass_k() {
-  return std::make_pair(rowpass_kernel<H, NW, R, FDW2, KX, true>, rowpass_kernel<H, NW, R, FDW2, KX>);
+  return std::make_pair(rowpass_kernel<H, NW, R, FDW2, KX, HANDOFF, true>, rowpass_kernel<H, NW, R, FDW2, KX, HANDOFF>);
 }
 
 // ---------------------------------------------------------------------------
@@ -2816,13 +2980,26 @@ static bool cs_fits(int mb) {
   return (2 * ((mb + kRowsShort - 1) / kRowsShort) + 7) / 8 * 32 <= resident;
 }
 
+// how the phases of the 32-row H 256 k-packed rowpass wait for each other
+// (satrl_ppo_rowpass_sync): 0 workgroup barriers, 1 LDS hand-offs (RpHandoff).
+// The hand-offs are the default: in-graph step at mb 4096 41.46-41.63 against
+// 42.09-42.26 us over four alternations of 24 000 steps each, bench.py's
+// update 39.32-39.43 against 40.24-40.33 us per step and its value +2.0-2.5 %
+// in every pair; mb 512 (other kernels) unchanged (EXPERIMENTS.md, "Rowpass H 256:
+// per-chunk LDS hand-offs")
+#ifndef SATRL_RP_SYNC_DEFAULT
+#define SATRL_RP_SYNC_DEFAULT 1
+#endif
+static std::atomic<int> g_rp_sync{SATRL_RP_SYNC_DEFAULT};
+
 // every rowpass launch: fdw2 (H <= 128) writes the block's dW2 partial to p2
 // instead of H1 / dZ2; ratio (nullable) receives the actor's per-row ratio
 static int launch_rowpass(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
                           const void* W2X, float epsilon, float ent_coef, float max_action, float* H1, float* dZ2,
                           float* ptail, float* pw1, float* p2, float* ratio, bool fdw2, void* stream,
-                          bool kx = false) {
-  const int R = rows_per_wg(H, mb), nrb = n_head_wg(H, mb);
+                          bool kx = false, bool long_rows = false) {
+  // (long_rows: 32-row blocks whatever the minibatch, satrl_ppo_rowpass_kx32)
+  const int R = long_rows ? kRows : rows_per_wg(H, mb), nrb = (mb + R - 1) / R;
   dim3 g((net < 0 ? 2 : 1) * nrb);   // (row block, net) pairs, or row blocks of one net
   // waves per workgroup: one 16-column tile per wave for both 16-row tiles
   const float inv_mb = 1.0f / (float)mb;
@@ -2851,6 +3028,8 @@ static int launch_rowpass(int H, int mb, int net, const float* src, const int64_
                 reinterpret_cast<unsigned short*>(dZ2), ptail, pw1, inv_mb);
   else if (kx && R == kRowsShort)
     rp(rowpass_k<256, 16, kRowsShort, false, true>());
+  else if (kx && g_rp_sync.load(std::memory_order_relaxed) == 1)
+    rp(rowpass_k<256, kNW256, kRows, false, true, true>());
   else if (kx)
     rp(rowpass_k<256, kNW256, kRows, false, true>());
   else if (R == kRowsShort)
@@ -2909,6 +3088,22 @@ int satrl_ppo_rowpass_kx(int H, int mb, int net, const float* src, const int64_t
   if (!kx_fits(H, mb, net, kx_elems, "satrl_ppo_rowpass_kx")) return -1;
   return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, static_cast<float*>(H1x),
                         static_cast<float*>(dZ2x), ptail, pw1, nullptr, nullptr, false, stream, true);
+}
+
+int satrl_ppo_rowpass_kx32(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
+                           const void* W2X, float epsilon, float ent_coef, float max_action, void* H1x, void* dZ2x,
+                           int64_t kx_elems, float* ptail, float* pw1, float* ratio, void* stream) {
+  if (H != 256 || mb <= 0 || net < -1 || net > 1 || !src || !P || !W2X || !H1x || !dZ2x ||
+      !ptail || !pw1)
+    return -1;
+  if (!kx_fits(H, mb, net, kx_elems, "satrl_ppo_rowpass_kx32")) return -1;
+  return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, static_cast<float*>(H1x),
+                        static_cast<float*>(dZ2x), ptail, pw1, nullptr, ratio, false, stream, true, true);
+}
+
+int satrl_ppo_rowpass_sync(int mode) {
+  if (mode < -1 || mode > 1) return -1;
+  return mode < 0 ? g_rp_sync.load(std::memory_order_relaxed) : g_rp_sync.exchange(mode, std::memory_order_relaxed);
 }
 
 int satrl_ppo_rowpass_error(int* err, double timeout_s, void* stream) {

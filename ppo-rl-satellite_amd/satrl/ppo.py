@@ -346,8 +346,8 @@ def rowpass_exchange_check(stream=None, timeout_s=None):
     t = _dist.dp_timeout_s() if timeout_s is None else float(timeout_s)
     check(L.satrl_ppo_rowpass_error(C.byref(e), t, stream_ptr(stream)), "satrl_ppo_rowpass_error")
     if e.value:
-        raise RuntimeError("satrl_ppo_rowpass_kx: a column-split exchange timed out (its workgroups were not "
-                           "resident together); the update is invalid")
+        raise RuntimeError("satrl_ppo_rowpass_kx: a column-split exchange (its workgroups were not resident "
+                           "together) or an LDS hand-off of the 32-row kernel timed out; the update is invalid")
 
 
 def uses_column_split(H, mb, B):
@@ -358,6 +358,30 @@ def uses_column_split(H, mb, B):
     mb = min(int(mb), int(B))
     tail = int(B) % mb if mb > 0 else 0
     return H == 256 and mb > 0 and (mb <= 1024 or 0 < tail <= 1024)
+
+
+def rowpass_sync(mode=None):
+    """satrl_ppo_rowpass_sync (include/satrl_ppo.h), a development switch:
+    how the phases of the 32-row H = 256 k-packed rowpass wait for each other,
+    0 workgroup barriers, 1 per-chunk LDS hand-offs (bitwise the same
+    outputs).  Sets the process-wide mode (None: only queries) and returns the
+    previous one; a captured graph keeps the form it was captured with."""
+    L = _lib.lib()
+    if _lib.LIB_PATH != _lib._PRODUCT_LIB and not hasattr(L, "satrl_ppo_rowpass_sync"):
+        return 0                             # (an older development build: A/B only)
+    prev = L.satrl_ppo_rowpass_sync(-1 if mode is None else int(mode))
+    if prev < 0:
+        raise ValueError(f"rowpass_sync: mode {mode!r} is not 0 or 1")
+    return prev
+
+
+def uses_handoff(H, mb, B):
+    """True when an update of B rows in minibatches of mb runs the hand-off
+    form of the 32-row rowpass (H = 256, minibatches above 1024 rows -- a
+    longer ragged tail has them too -- and rowpass_sync() == 1): its bounded
+    waits report through the same error word, so such updates run
+    rowpass_exchange_check too."""
+    return H == 256 and min(int(mb), int(B)) > 1024 and rowpass_sync() == 1
 
 
 class FusedMinibatch:
@@ -937,8 +961,8 @@ class PPOLearner:
                 break
         if self.peer is not None:
             self.peer.check()                # a peer's value never arrived: the update is invalid
-        if uses_column_split(self.H, self.mini_batch_size, B):
-            rowpass_exchange_check()         # (minibatches / tails <= 1024 rows; bounded by the DP deadline)
+        if uses_column_split(self.H, self.mini_batch_size, B) or uses_handoff(self.H, self.mini_batch_size, B):
+            rowpass_exchange_check()         # (a kernel's bounded wait ran out; bounded by the DP deadline)
         if self.use_lr_decay:
             self.lr_decay(total_steps)
 

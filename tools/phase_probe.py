@@ -9,7 +9,9 @@ Stamps (ppo_kernels.hip PHASE_PROBE): 0 start, 8 gather issued, 9 S ready,
 10 fc1 MFMA, 11 tanh(fc1) stored, 1 barrier, 2 fc2 MFMA (B), 3 output-layer
 sums (C fwd), 12 head: out_sum/tanh/logp, 13 head: ratio..dz/dls, 14 head:
 dz3s + row sums (12-14 wave 0 only), 4 loss head, 5 dZ2 + tail partials,
-6 dH1 MFMA (D), 7 end (E).
+6 dH1 MFMA (D), 7 end (E).  1, 4 and 5 are "the wave passed the wait": behind
+the barrier, or in the hand-off form (satrl_ppo_rowpass_sync 1, the default)
+behind the wait for B's first chunk (1), for dz3s (4) and for D's first chunk (5).
 """
 import ctypes as C
 import os

@@ -4,7 +4,9 @@ time (event-timed graph replays of the update, 16-minibatch groups) and each
 kernel's live launch span (satrl_span_probe: max wave exit - min wave start)
 inside those graphs, for the library SATRL_LIB_PATH selects (default: the
 product build).  Optional: the rollout's policy and env-step spans.
-Usage: python tools/span_time.py H mb[,mb...] [reps] [rollout]"""
+Usage: [SPAN_REPLAYS=n] python tools/span_time.py H mb[,mb...] [reps] [rollout]
+SPAN_REPLAYS: graph replays (of 16 steps) in the timed window, default 20 (14 ms
+at mb 4096: process-to-process spread 0.7 us); 1500 (a second) resolves 0.2 us."""
 import os
 import sys
 
@@ -17,9 +19,10 @@ from satrl.spans import SpanProbe  # noqa: E402
 from satrl.trainer import args_param  # noqa: E402
 
 tag = os.path.basename(os.environ.get("SATRL_LIB_PATH", "product"))
+REPLAYS = int(os.environ.get("SPAN_REPLAYS", "20"))
 
 
-def step_and_spans(H, mb, n=20):
+def step_and_spans(H, mb, n=REPLAYS):
     B = 16 * mb
     a = args_param(hidden_width=H, mini_batch_size=mb, batch_size=B, chkpt_dir="/tmp")
     L = PPOLearner(a, "pursuer", graph_group=16)
@@ -78,7 +81,8 @@ if __name__ == "__main__":
             step, s, gp = step_and_spans(H, mb)
             ks = " ".join(f"{k} {v['median_us']:.2f}" for k, v in s.items())
             gs = " ".join(f"{k} {v['median_us']:.2f}" for k, v in gp.items())
-            print(f"[{tag}] H {H} mb {mb:5d}: step {step:6.2f} us | span medians: {ks} | gaps: {gs}", flush=True)
+            win = f" ({REPLAYS} replays of 16)" if REPLAYS != 20 else ""
+            print(f"[{tag}] H {H} mb {mb:5d}: step {step:6.2f} us{win} | span medians: {ks} | gaps: {gs}", flush=True)
     if len(sys.argv) > 4 and sys.argv[4] == "rollout":
         step, s = rollout_spans(H)
         ks = " ".join(f"{k} {v['median_us']:.2f}" for k, v in s.items())
