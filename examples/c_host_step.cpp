@@ -112,8 +112,13 @@ void ppo_step(const std::string& out, int mb, hipStream_t st) {
     if (b1 == 1.0 && b2 == 1.0) break;
   }
   const std::vector<float> lr = {2e-4f, 2e-4f};
-  int64_t nwg = 0, nblk = 0;
-  PPO_OK(satrl_ppo_sizes(H, mb, &nwg, &nblk));
+  // the library's plan of this step: its kernels (KX at H = 256) and every buffer's size
+  satrl_ppo_plan plan;
+  PPO_OK(satrl_ppo_step_plan(H, mb, -1, &plan));
+  if (plan.step != SATRL_PPO_STEP_KX) {
+    std::fprintf(stderr, "c_host_step: the launch sequence below is the k-packed step\n");
+    std::exit(1);
+  }
 
   float* d_P = dev(P);
   // the fc2 operand image (the f32 fc2.weight^T), built on the device from P
@@ -124,26 +129,26 @@ void ppo_step(const std::string& out, int mb, hipStream_t st) {
   float* d_V = dev<float>(total);
   float* d_G = dev<float>(total);
   float* d_src = dev(src);
-  float* d_H1 = dev<float>(2 * (size_t)mb * H);
-  float* d_dZ2 = dev<float>(2 * (size_t)mb * H);
-  float* d_pt = dev<float>((size_t)nwg * (6 * H + 12));
-  float* d_pw = dev<float>((size_t)nwg * 2 * H * 20);
-  double* d_nsq = dev<double>(2 * (size_t)nblk);
+  float* d_H1 = dev<float>((size_t)plan.rows_floats);
+  float* d_dZ2 = dev<float>((size_t)plan.rows_floats);
+  float* d_pt = dev<float>((size_t)plan.ptail_floats);
+  float* d_pw = dev<float>((size_t)plan.pw1_floats);
+  double* d_nsq = dev<double>(2 * (size_t)plan.norm_blocks);
   double* d_steps = dev<double>(2);
   double* d_bct = dev(bct);
   float* d_lr = dev(lr);
 
   PPO_OK(satrl_ppo_rowpass(H, mb, -1, d_src, nullptr, d_P, d_W2X, 0.1f, 0.01f, 1.6f, d_H1, d_dZ2, d_pt, d_pw, st));
   HIP_OK(hipStreamSynchronize(st));
-  save(out, (tag + "H1.f32").c_str(), host(d_H1, 2 * (size_t)mb * H));
-  save(out, (tag + "dZ2.f32").c_str(), host(d_dZ2, 2 * (size_t)mb * H));
+  save(out, (tag + "H1.f32").c_str(), host(d_H1, (size_t)plan.rows_floats));
+  save(out, (tag + "dZ2.f32").c_str(), host(d_dZ2, (size_t)plan.rows_floats));
   // the product step: the rowpass with k-packed bf16 H1 / dZ2 planes and the
   // split-bf16 dW2 on them (every kernel hand-written, no library tiles)
-  const int64_t kxe = satrl_ppo_kx_elems(H, mb);
+  const int64_t kxe = plan.kx_elems;
   uint16_t* d_H1x = dev<uint16_t>((size_t)kxe);
   uint16_t* d_dZ2x = dev<uint16_t>((size_t)kxe);
-  const int S = satrl_ppo_dw2_kx_splits(H, mb, -1);
-  const int64_t p2n = 2LL * S * H * H;          // every slab call takes these capacities and refuses past them
+  const int S = plan.splits;
+  const int64_t p2n = plan.p2_floats;           // every slab call takes these capacities and refuses past them
   float* d_p2 = dev<float>((size_t)p2n);
   PPO_OK(satrl_ppo_rowpass_kx(H, mb, -1, d_src, nullptr, d_P, d_W2X, 0.1f, 0.01f, 1.6f, d_H1x, d_dZ2x, kxe, d_pt,
                               d_pw, st));
@@ -152,12 +157,13 @@ void ppo_step(const std::string& out, int mb, hipStream_t st) {
   PPO_OK(satrl_ppo_reduce(H, mb, -1, S, 3 | 4, d_p2, p2n, nullptr, nullptr, d_G, d_nsq, d_steps, st));
   PPO_OK(satrl_ppo_adam(H, mb, -1, d_nsq, d_steps, d_bct, (int)(bct.size() / 2), d_lr, 0.9f, 0.999f, 1e-5f, 0.5f, 1,
                         d_G, d_P, d_M, d_V, d_W2X, st));
-  // up to 1024 rows the rowpass ran the column-split kernel: its in-launch
-  // exchange must not have timed out (the call waits for the stream, 60 s at most)
+  // a rowpass with bounded waits inside the launch (plan.error_word: the
+  // column split, the LDS hand-offs): none may have timed out (the call waits
+  // for the stream, 60 s at most)
   int xerr = 0;
   PPO_OK(satrl_ppo_rowpass_error(&xerr, 60.0, st));
   if (xerr) {
-    std::fprintf(stderr, "c_host_step: the column-split rowpass exchange timed out\n");
+    std::fprintf(stderr, "c_host_step: a bounded wait of the rowpass timed out\n");
     std::exit(1);
   }
   save(out, (tag + "P0.f32").c_str(), P);

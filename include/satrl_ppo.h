@@ -43,6 +43,42 @@ int satrl_ppo_layout(int H, int64_t* offsets /* [SATRL_PPO_NOFF] */);
  * minibatch of mb rows -- or of any shorter one -- writes, and of norm blocks */
 int satrl_ppo_sizes(int H, int mb, int64_t* n_head_wg, int64_t* n_norm_blocks);
 
+/* The plan of the product's minibatch step for (H, mb, net): which kernels
+ * run and what every buffer must hold.  Host arithmetic only, no device call;
+ * the one statement of every rule that picks a kernel or sizes a buffer (the
+ * launches below take their kernel from it, satrl_ppo_sizes / _row_blocks /
+ * _kx_elems / _dw2_kx_splits are reads of it).  A host sizes its buffers from
+ * the plan of its longest minibatch and steps each minibatch, a ragged tail
+ * too, with the `splits` of that minibatch's own plan.                     */
+enum { SATRL_PPO_STEP_ROWS = 0,   /* rowpass -> dw2 -> reduce -> adam                       (H 128) */
+       SATRL_PPO_STEP_FUSED,      /* rowpass_dw2 -> reduce -> adam                          (H 64)  */
+       SATRL_PPO_STEP_KX };       /* rowpass_kx -> dw2_kx_w1 -> reduce(mode | 4) -> adam    (H 256) */
+enum { SATRL_PPO_RP_WG32 = 0,     /* 32-row workgroups, workgroup barriers                          */
+       SATRL_PPO_RP_WG16,         /* 16-row 16-wave workgroups                                      */
+       SATRL_PPO_RP_CS,           /* column split when its grid is resident, else WG16 (same bits)  */
+       SATRL_PPO_RP_WG32_HANDOFF };  /* 32-row workgroups, per-chunk LDS hand-offs                  */
+typedef struct satrl_ppo_plan {
+  int step, rowpass;              /* the enums above, for the product step of (H, mb, net)          */
+  int rows_per_block, row_blocks; /* this minibatch                                                 */
+  int splits;                     /* S of this minibatch's dW2 / reduce                             */
+  int error_word;                 /* 1: the rowpass may set the word satrl_ppo_rowpass_error reads  */
+  /* capacities that hold this minibatch AND every shorter one (a ragged tail), both nets:          */
+  int64_t slab_blocks, norm_blocks, max_splits;
+  int64_t ptail_floats, pw1_floats, p2_floats, kx_elems /* 0 unless KX */, rows_floats /* H1 or dZ2 f32 */;
+} satrl_ppo_plan;
+/* rowpass: the kernel satrl_ppo_rowpass_kx (KX), satrl_ppo_rowpass_dw2 (FUSED)
+ * or satrl_ppo_rowpass (ROWS) launches for (H, mb, net), under the current
+ * satrl_ppo_rowpass_sync mode; whether a column-split grid is resident is
+ * settled at the launch, not here.  splits: satrl_ppo_row_blocks (FUSED),
+ * satrl_ppo_dw2_splits (ROWS, the both-nets count for every net) or
+ * satrl_ppo_dw2_kx_splits(H, mb, net) (KX).  max_splits >= the splits of every
+ * minibatch of at most mb rows for this net: slab_blocks (FUSED), else at
+ * least the dW2 kernel's workgroup target over its output tiles.  ptail_floats
+ * = slab_blocks * (6H + 12), pw1_floats = slab_blocks * 2 * H * 20, p2_floats
+ * = 2 * max_splits * H * H, rows_floats = 2 * mb * H, kx_elems per plane
+ * buffer.  -1: H not 64/128/256, mb <= 0, net not -1/0/1 or a NULL plan.    */
+int satrl_ppo_step_plan(int H, int mb, int net, satrl_ppo_plan* plan);
+
 /* `net` (rowpass, reduce, adam): -1 = actor and critic in one launch, 0 =
  * actor only, 1 = critic only.  The two nets share nothing in a minibatch
  * step but the rows, and a one-net call touches only that net's elements
@@ -53,9 +89,10 @@ int satrl_ppo_sizes(int H, int mb, int64_t* n_head_wg, int64_t* n_norm_blocks);
  * slabs p2 [2][S][H][H] (f32 MFMA, fixed summation order) from the f32 rows
  * satrl_ppo_rowpass writes, at every width.  S must be
  * satrl_ppo_dw2_splits(H, mb) (about one workgroup per CU, no empty split).
- * The product paths: H = 64 / 128 fuse the product into the rowpass
- * (satrl_ppo_rowpass_dw2), H = 256 runs it from k-packed planes
- * (satrl_ppo_rowpass_kx + satrl_ppo_dw2_kx).                              */
+ * The product paths (satrl_ppo_step_plan's step): H = 128 runs this entry
+ * (ROWS), H = 64 fuses the product into the rowpass (FUSED,
+ * satrl_ppo_rowpass_dw2, which H = 128 can run too), H = 256 runs it from
+ * k-packed planes (KX, satrl_ppo_rowpass_kx + satrl_ppo_dw2_kx_w1).       */
 int satrl_ppo_dw2_splits(int H, int mb);
 /* Capacities (every call that writes or reads the dW2 slabs or the k-packed
  * planes takes the caller's buffer size and refuses with -1, before any

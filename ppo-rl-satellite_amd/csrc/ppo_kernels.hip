@@ -2176,9 +2176,10 @@ __global__ void __launch_bounds__(256) dw2_kx_kernel(int mb, int S, int KR, int 
 // the reduce and the boundary before it; at mb 1024 slower, 37.2 against
 // 35.6; EXPERIMENTS.md round 6)
 constexpr int kKxWgs = 256, kKxHalfMb = 512;
+int kx_tiles(int net) { return (net < 0 ? 2 : 1) * (256 / kKxTW) * (256 / kKxTW); }   // output tiles per split
 int kx_splits(int mb, int net) {
   const int target = mb <= kKxHalfMb ? kKxWgs / 2 : kKxWgs;
-  const int tiles = (net < 0 ? 2 : 1) * (256 / kKxTW) * (256 / kKxTW), nch = (int)(kx_rows(mb) / 32);
+  const int tiles = kx_tiles(net), nch = (int)(kx_rows(mb) / 32);
   int S = target / tiles;
   if (S > nch) S = nch;
   if (S < 1) S = 1;
@@ -2186,9 +2187,11 @@ int kx_splits(int mb, int net) {
   return (nch + cps - 1) / cps;
 }
 
+// split-K ways of dw2_kernel: about kDwWgs workgroups, no empty split
+constexpr int kDwWgs = 256;
+int dw2_tiles(int H, int net) { return (net < 0 ? 2 : 1) * (H / 64) * (H / 64); }
 int dw2_splits(int H, int mb, int net) {
-  const int tiles = (net < 0 ? 2 : 1) * (H / 64) * (H / 64);
-  int S = 256 / tiles;
+  int S = kDwWgs / dw2_tiles(H, net);
   const int maxS = (mb + kDwKC - 1) / kDwKC;
   if (S > maxS) S = maxS;
   if (S < 1) S = 1;
@@ -2956,10 +2959,87 @@ int satrl_ppo_layout(int H, int64_t* off) {
   return 0;
 }
 
+// how the phases of the 32-row H 256 k-packed rowpass wait for each other
+// (satrl_ppo_rowpass_sync): 0 workgroup barriers, 1 LDS hand-offs (RpHandoff).
+// The hand-offs are the default: in-graph step at mb 4096 41.46-41.63 against
+// 42.09-42.26 us over four alternations of 24 000 steps each, bench.py's
+// update 39.32-39.43 against 40.24-40.33 us per step and its value +2.0-2.5 %
+// in every pair; mb 512 (other kernels) unchanged (EXPERIMENTS.md, "Rowpass H 256:
+// per-chunk LDS hand-offs")
+#ifndef SATRL_RP_SYNC_DEFAULT
+#define SATRL_RP_SYNC_DEFAULT 1
+#endif
+static std::atomic<int> g_rp_sync{SATRL_RP_SYNC_DEFAULT};
+
+// ---------------------------------------------------------------------------
+// The step plan (satrl_ppo_step_plan): which kernels step a minibatch and what
+// their buffers hold, host arithmetic only.  launch_rowpass takes its kernel
+// from rowpass_kind and the size queries of the ABI read plan_fill, so a
+// threshold changes here and nowhere else.
+// ---------------------------------------------------------------------------
+// what a rowpass hands to dW2: f32 H1 / dZ2 rows, its own dW2 slabs (p2), or k-packed planes
+enum RpOut { kRpOutRows, kRpOutDw2, kRpOutPlanes };
+// row blocks by minibatch size, or 32-row blocks whatever the size (satrl_ppo_rowpass_kx32)
+enum RpBlock { kRpBlockByMb, kRpBlock32 };
+
+static int step_kind(int H) {
+  return H == 64 ? SATRL_PPO_STEP_FUSED : H == 128 ? SATRL_PPO_STEP_ROWS : SATRL_PPO_STEP_KX;
+}
+static RpOut step_out(int step) {
+  return step == SATRL_PPO_STEP_FUSED ? kRpOutDw2 : step == SATRL_PPO_STEP_KX ? kRpOutPlanes : kRpOutRows;
+}
+static int rp_rows(int kind) { return kind == SATRL_PPO_RP_WG16 || kind == SATRL_PPO_RP_CS ? kRowsShort : kRows; }
+// the rowpass kernel (SATRL_PPO_RP_*) of one launch.  Only the k-packed H 256
+// rowpass has more than the two block heights: the column split for both nets
+// up to kCsMaxMb rows, the hand-off form of the 32-row kernel by the switch.
+static int rowpass_kind(int H, int mb, int net, RpOut out, RpBlock block) {
+  const int R = block == kRpBlock32 ? kRows : rows_per_wg(H, mb);
+  if (H != 256 || out != kRpOutPlanes) return R == kRowsShort ? SATRL_PPO_RP_WG16 : SATRL_PPO_RP_WG32;
+  if (R == kRowsShort) return net < 0 && mb <= kCsMaxMb ? SATRL_PPO_RP_CS : SATRL_PPO_RP_WG16;
+  return g_rp_sync.load(std::memory_order_relaxed) == 1 ? SATRL_PPO_RP_WG32_HANDOFF : SATRL_PPO_RP_WG32;
+}
+// (H, mb, net checked by the caller)
+static void plan_fill(int H, int mb, int net, satrl_ppo_plan* p) {
+  const Layout L = layout(H);
+  p->step = step_kind(H);
+  p->rowpass = rowpass_kind(H, mb, net, step_out(p->step), kRpBlockByMb);
+  p->rows_per_block = rp_rows(p->rowpass);
+  p->row_blocks = n_head_wg(H, mb);
+  p->error_word = p->rowpass == SATRL_PPO_RP_CS || p->rowpass == SATRL_PPO_RP_WG32_HANDOFF;
+  p->slab_blocks = n_head_wg_cap(H, mb);                          // >= every minibatch of <= mb rows
+  p->norm_blocks = n_blocks(geom(H, mb, 1, -1));                  // >= the per-net counts
+  // splits of this minibatch, and their bound over every shorter one: a
+  // shorter minibatch can split more ways (whole chunks, no empty split), but
+  // never more ways than the workgroup target over the output tiles allows
+  if (p->step == SATRL_PPO_STEP_FUSED) {                          // one slab per row block
+    p->splits = p->row_blocks;
+    p->max_splits = p->slab_blocks;
+  } else if (p->step == SATRL_PPO_STEP_KX) {
+    p->splits = kx_splits(mb, net);
+    p->max_splits = std::max(p->splits, kKxWgs / kx_tiles(net));
+  } else {                                                        // (both nets' count: a one-net call uses the same)
+    p->splits = dw2_splits(H, mb, -1);
+    p->max_splits = std::max(p->splits, kDwWgs / dw2_tiles(H, -1));
+  }
+  p->ptail_floats = p->slab_blocks * L.tail;
+  p->pw1_floats = p->slab_blocks * 2 * H * 20;
+  p->p2_floats = 2 * p->max_splits * H * H;
+  p->kx_elems = p->step == SATRL_PPO_STEP_KX ? 2LL * 3 * kx_rows(mb) * H : 0;
+  p->rows_floats = 2LL * mb * H;
+}
+
+int satrl_ppo_step_plan(int H, int mb, int net, satrl_ppo_plan* plan) {
+  if (!valid_h(H) || mb <= 0 || net < -1 || net > 1 || !plan) return -1;
+  plan_fill(H, mb, net, plan);
+  return 0;
+}
+
 int satrl_ppo_sizes(int H, int mb, int64_t* nwg, int64_t* nblk) {
   if (!valid_h(H) || mb <= 0) return -1;
-  if (nwg) *nwg = n_head_wg_cap(H, mb);                         // >= every minibatch of <= mb rows
-  if (nblk) *nblk = n_blocks(geom(H, mb, 1, -1));                 // >= the per-net counts
+  satrl_ppo_plan p;
+  plan_fill(H, mb, -1, &p);
+  if (nwg) *nwg = p.slab_blocks;
+  if (nblk) *nblk = p.norm_blocks;
   return 0;
 }
 
@@ -2980,33 +3060,23 @@ static bool cs_fits(int mb) {
   return (2 * ((mb + kRowsShort - 1) / kRowsShort) + 7) / 8 * 32 <= resident;
 }
 
-// how the phases of the 32-row H 256 k-packed rowpass wait for each other
-// (satrl_ppo_rowpass_sync): 0 workgroup barriers, 1 LDS hand-offs (RpHandoff).
-// The hand-offs are the default: in-graph step at mb 4096 41.46-41.63 against
-// 42.09-42.26 us over four alternations of 24 000 steps each, bench.py's
-// update 39.32-39.43 against 40.24-40.33 us per step and its value +2.0-2.5 %
-// in every pair; mb 512 (other kernels) unchanged (EXPERIMENTS.md, "Rowpass H 256:
-// per-chunk LDS hand-offs")
-#ifndef SATRL_RP_SYNC_DEFAULT
-#define SATRL_RP_SYNC_DEFAULT 1
-#endif
-static std::atomic<int> g_rp_sync{SATRL_RP_SYNC_DEFAULT};
-
-// every rowpass launch: fdw2 (H <= 128) writes the block's dW2 partial to p2
-// instead of H1 / dZ2; ratio (nullable) receives the actor's per-row ratio
+// every rowpass launch: `out` says what it writes for dW2 (kRpOutDw2, H <= 128:
+// the block's dW2 partial to p2 instead of H1 / dZ2; kRpOutPlanes, H = 256: H1 /
+// dZ2 are the k-packed planes); ratio (nullable) receives the actor's per-row ratio
 static int launch_rowpass(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
                           const void* W2X, float epsilon, float ent_coef, float max_action, float* H1, float* dZ2,
-                          float* ptail, float* pw1, float* p2, float* ratio, bool fdw2, void* stream,
-                          bool kx = false, bool long_rows = false) {
-  // (long_rows: 32-row blocks whatever the minibatch, satrl_ppo_rowpass_kx32)
-  const int R = long_rows ? kRows : rows_per_wg(H, mb), nrb = (mb + R - 1) / R;
+                          float* ptail, float* pw1, float* p2, float* ratio, RpOut out, RpBlock block, void* stream) {
+  // the plan's kernel; the column split only when its grid is resident (else
+  // the 16-wave kernel on the same 16-row blocks: the same bits)
+  int kind = rowpass_kind(H, mb, net, out, block);
+  if (kind == SATRL_PPO_RP_CS && !cs_fits(mb)) kind = SATRL_PPO_RP_WG16;
+  const bool cs = kind == SATRL_PPO_RP_CS, fdw2 = out == kRpOutDw2, kx = out == kRpOutPlanes;
+  const int R = rp_rows(kind), nrb = (mb + R - 1) / R;
   dim3 g((net < 0 ? 2 : 1) * nrb);   // (row block, net) pairs, or row blocks of one net
   // waves per workgroup: one 16-column tile per wave for both 16-row tiles
   const float inv_mb = 1.0f / (float)mb;
   const int nw = H == 64 ? 4 : H == 128 ? 8 : 16;                  // waves per workgroup
-  // (H = 256, k-packed, both nets, mb <= kCsMaxMb: the column-split kernel,
-  // groups of kCsSplit workgroups dealt in windows of 32 blocks)
-  const bool cs = H == 256 && kx && R == kRowsShort && net < 0 && cs_fits(mb);
+  // (the column-split kernel: groups of kCsSplit workgroups dealt in windows of 32 blocks)
   const dim3 gc((unsigned)((2 * nrb + 7) / 8 * 32));
   unsigned long long* sp =
       satrl_span::take(satrl_span::kRowpass, cs ? (int64_t)gc.x * kCsWaves : (int64_t)g.x * nw);
@@ -3014,28 +3084,20 @@ static int launch_rowpass(int H, int mb, int net, const float* src, const int64_
     launch_span(k.first, k.second, sp, g, dim3(nw * 64), stream, mb, net, src, idx, P, W2X, H1, dZ2, epsilon,
                 ent_coef, max_action, ptail, pw1, p2, nrb, ratio, inv_mb);
   };
-  if (H == 64 && fdw2)
-    rp(rowpass_k<64, 4, kRows, true, false>());
-  else if (H == 64)
-    rp(rowpass_k<64, 4, kRows, false, false>());
-  else if (H == 128 && fdw2)
-    rp(rowpass_k<128, 8, kRows, true, false>());
+  if (H == 64)
+    fdw2 ? rp(rowpass_k<64, 4, kRows, true, false>()) : rp(rowpass_k<64, 4, kRows, false, false>());
   else if (H == 128)
-    rp(rowpass_k<128, 8, kRows, false, false>());
+    fdw2 ? rp(rowpass_k<128, 8, kRows, true, false>()) : rp(rowpass_k<128, 8, kRows, false, false>());
   else if (cs)
     launch_span(rowpass_cs_kernel<true>, rowpass_cs_kernel<false>, sp, gc, dim3(kCsWaves * 64), stream, mb, src, idx, P,
                 static_cast<const float*>(W2X), epsilon, ent_coef, max_action, reinterpret_cast<unsigned short*>(H1),
                 reinterpret_cast<unsigned short*>(dZ2), ptail, pw1, inv_mb);
-  else if (kx && R == kRowsShort)
-    rp(rowpass_k<256, 16, kRowsShort, false, true>());
-  else if (kx && g_rp_sync.load(std::memory_order_relaxed) == 1)
+  else if (kind == SATRL_PPO_RP_WG16)
+    kx ? rp(rowpass_k<256, 16, kRowsShort, false, true>()) : rp(rowpass_k<256, 16, kRowsShort, false, false>());
+  else if (kind == SATRL_PPO_RP_WG32_HANDOFF)
     rp(rowpass_k<256, kNW256, kRows, false, true, true>());
-  else if (kx)
-    rp(rowpass_k<256, kNW256, kRows, false, true>());
-  else if (R == kRowsShort)
-    rp(rowpass_k<256, 16, kRowsShort, false, false>());
   else
-    rp(rowpass_k<256, kNW256, kRows, false, false>());
+    kx ? rp(rowpass_k<256, kNW256, kRows, false, true>()) : rp(rowpass_k<256, kNW256, kRows, false, false>());
   LAUNCH_CHECK();
   return 0;
 }
@@ -3046,7 +3108,7 @@ int satrl_ppo_rowpass(int H, int mb, int net, const float* src, const int64_t* i
   if (!valid_h(H) || mb <= 0 || net < -1 || net > 1 || !src || !P || !W2X || !H1 || !dZ2 || !ptail || !pw1)
     return -1;
   return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, H1, dZ2, ptail, pw1, nullptr,
-                        nullptr, false, stream);
+                        nullptr, kRpOutRows, kRpBlockByMb, stream);
 }
 
 int satrl_ppo_rowpass_ratio(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
@@ -3056,12 +3118,12 @@ int satrl_ppo_rowpass_ratio(int H, int mb, int net, const float* src, const int6
       !ratio)
     return -1;
   return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, H1, dZ2, ptail, pw1, nullptr,
-                        ratio, false, stream);
+                        ratio, kRpOutRows, kRpBlockByMb, stream);
 }
 
 int satrl_ppo_row_blocks(int H, int mb) {
-  if (!valid_h(H) || mb <= 0) return -1;
-  return n_head_wg(H, mb);
+  satrl_ppo_plan p;
+  return satrl_ppo_step_plan(H, mb, -1, &p) == 0 ? p.row_blocks : -1;
 }
 
 int satrl_ppo_rowpass_dw2(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
@@ -3071,12 +3133,12 @@ int satrl_ppo_rowpass_dw2(int H, int mb, int net, const float* src, const int64_
     return -1;
   if (!p2_fits(H, net, n_head_wg(H, mb), p2_floats, "satrl_ppo_rowpass_dw2")) return -1;   // one slab per row block
   return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, nullptr, nullptr, ptail, pw1, p2,
-                        nullptr, true, stream);
+                        nullptr, kRpOutDw2, kRpBlockByMb, stream);
 }
 
 int64_t satrl_ppo_kx_elems(int H, int mb) {
-  if (H != 256 || mb <= 0) return -1;
-  return 2LL * 3 * kx_rows(mb) * H;
+  satrl_ppo_plan p;
+  return H == 256 && satrl_ppo_step_plan(H, mb, -1, &p) == 0 ? p.kx_elems : -1;
 }
 
 int satrl_ppo_rowpass_kx(int H, int mb, int net, const float* src, const int64_t* idx, const float* P, const void* W2X,
@@ -3087,7 +3149,7 @@ int satrl_ppo_rowpass_kx(int H, int mb, int net, const float* src, const int64_t
     return -1;
   if (!kx_fits(H, mb, net, kx_elems, "satrl_ppo_rowpass_kx")) return -1;
   return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, static_cast<float*>(H1x),
-                        static_cast<float*>(dZ2x), ptail, pw1, nullptr, nullptr, false, stream, true);
+                        static_cast<float*>(dZ2x), ptail, pw1, nullptr, nullptr, kRpOutPlanes, kRpBlockByMb, stream);
 }
 
 int satrl_ppo_rowpass_kx32(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
@@ -3098,7 +3160,7 @@ int satrl_ppo_rowpass_kx32(int H, int mb, int net, const float* src, const int64
     return -1;
   if (!kx_fits(H, mb, net, kx_elems, "satrl_ppo_rowpass_kx32")) return -1;
   return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, static_cast<float*>(H1x),
-                        static_cast<float*>(dZ2x), ptail, pw1, nullptr, ratio, false, stream, true, true);
+                        static_cast<float*>(dZ2x), ptail, pw1, nullptr, ratio, kRpOutPlanes, kRpBlock32, stream);
 }
 
 int satrl_ppo_rowpass_sync(int mode) {
@@ -3169,8 +3231,8 @@ int satrl_ppo_rowpass_fault_inject(int group, unsigned value, void* stream) {
 }
 
 int satrl_ppo_dw2_kx_splits(int H, int mb, int net) {
-  if (H != 256 || mb <= 0 || net < -1 || net > 1) return -1;
-  return kx_splits(mb, net);
+  satrl_ppo_plan p;
+  return H == 256 && satrl_ppo_step_plan(H, mb, net, &p) == 0 ? p.splits : -1;
 }
 
 int satrl_ppo_dw2_kx(int H, int mb, int net, int S, const void* H1x, const void* dZ2x, int64_t kx_elems, float* p2,
@@ -3180,7 +3242,7 @@ int satrl_ppo_dw2_kx(int H, int mb, int net, int S, const void* H1x, const void*
   if ((int64_t)cps * (S - 1) >= nch) return -1;                  // an empty split: use satrl_ppo_dw2_kx_splits
   if (!kx_fits(H, mb, net, kx_elems, "satrl_ppo_dw2_kx") || !p2_fits(H, net, S, p2_floats, "satrl_ppo_dw2_kx"))
     return -1;
-  const dim3 g((unsigned)((net < 0 ? 2 : 1) * (256 / kKxTW) * (256 / kKxTW) * S));
+  const dim3 g((unsigned)(kx_tiles(net) * S));
   unsigned long long* sp = satrl_span::take(satrl_span::kDw2, (int64_t)g.x * 4);
   launch_span(dw2_kx_kernel<kKxTW, true>, dw2_kx_kernel<kKxTW>, sp, g, dim3(256), stream, mb, S, cps * 32, net,
               static_cast<const unsigned short*>(H1x), static_cast<const unsigned short*>(dZ2x), p2);
@@ -3198,7 +3260,7 @@ int satrl_ppo_dw2_kx_w1(int H, int mb, int net, int S, const void* H1x, const vo
   if (!kx_fits(H, mb, net, kx_elems, "satrl_ppo_dw2_kx_w1") || !p2_fits(H, net, S, p2_floats, "satrl_ppo_dw2_kx_w1"))
     return -1;
   const RedGeom rg = geom(H, mb, S, net);
-  const int ndw = (net < 0 ? 2 : 1) * (256 / kKxTW) * (256 / kKxTW) * S;
+  const int ndw = kx_tiles(net) * S;
   const dim3 g((unsigned)(ndw + rg.nb1 + rg.nbt));
   unsigned long long* sp = satrl_span::take(satrl_span::kDw2, (int64_t)g.x * 4);
   const unsigned short *h1 = static_cast<const unsigned short*>(H1x), *dz = static_cast<const unsigned short*>(dZ2x);
@@ -3219,7 +3281,7 @@ int satrl_ppo_dw2(int H, int mb, int net, int S, const float* H1, const float* d
   const int KR = ((mb + S - 1) / S + kDwKC - 1) / kDwKC * kDwKC;
   if ((int64_t)KR * (S - 1) >= mb) return -1;                    // an empty split: use satrl_ppo_dw2_splits
   if (!p2_fits(H, net, S, p2_floats, "satrl_ppo_dw2")) return -1;
-  const dim3 g((unsigned)((net < 0 ? 2 : 1) * (H / 64) * (H / 64) * S));
+  const dim3 g((unsigned)(dw2_tiles(H, net) * S));
   hipStream_t st = (hipStream_t)stream;
   if (H == 64)
     hipLaunchKernelGGL(dw2_kernel<64>, g, dim3(256), 0, st, mb, S, KR, net, H1, dZ2, p2);

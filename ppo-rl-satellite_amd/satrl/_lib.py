@@ -19,9 +19,8 @@ import torch  # noqa: F401  (must be loaded before libsatrl.so, see module doc)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(os.path.dirname(PKG_DIR), "csrc")
-LIB_PATH = _PRODUCT_LIB = os.path.join(PKG_DIR, "libsatrl.so")
-# development A/B builds only (tools/_probe variants); the shipped path is LIB_PATH
-LIB_PATH = os.environ.get("SATRL_LIB_PATH", LIB_PATH)
+# (SATRL_LIB_PATH: a development A/B build of the current tree's ABI, tools/README.md)
+LIB_PATH = os.environ.get("SATRL_LIB_PATH", os.path.join(PKG_DIR, "libsatrl.so"))
 
 SATENV_F64_PLANES = 15
 SATENV_I32_PLANES = 3
@@ -43,6 +42,17 @@ class SatenvResetDist(C.Structure):
     """Mirror of ``satenv_reset_dist`` (include/satenv.h)."""
     _fields_ = [("lo", C.c_double * 12), ("hi", C.c_double * 12), ("seed", C.c_uint64), ("env_offset", C.c_int64),
                 ("enabled", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StepPlan(C.Structure):
+    """Mirror of ``satrl_ppo_plan`` (include/satrl_ppo.h)."""
+    _fields_ = ([(k, C.c_int) for k in ("step", "rowpass", "rows_per_block", "row_blocks", "splits", "error_word")] +
+                [(k, C.c_int64) for k in ("slab_blocks", "norm_blocks", "max_splits", "ptail_floats", "pw1_floats",
+                                          "p2_floats", "kx_elems", "rows_floats")])
+
+
+STEP_ROWS, STEP_FUSED, STEP_KX = range(3)                       # satrl_ppo_plan.step
+RP_WG32, RP_WG16, RP_CS, RP_WG32_HANDOFF = range(4)             # satrl_ppo_plan.rowpass
 
 
 class NativeError(RuntimeError):
@@ -126,6 +136,7 @@ _SIGS = {
     "satrl_last_error": ([], C.c_char_p),
     "satrl_ppo_layout": ([C.c_int, C.POINTER(_i64)], C.c_int),
     "satrl_ppo_sizes": ([C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)], C.c_int),
+    "satrl_ppo_step_plan": ([C.c_int, C.c_int, C.c_int, C.POINTER(StepPlan)], C.c_int),
     "satrl_ppo_dw2_splits": ([C.c_int, C.c_int], C.c_int),
     "satrl_ppo_dw2": ([C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _i64, _vp], C.c_int),
     "satrl_ppo_reduce": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -197,9 +208,10 @@ def lib():
         except OSError as e:
             raise NativeError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (argt, rest) in _SIGS.items():
-            if LIB_PATH != _PRODUCT_LIB and not hasattr(L, name):
-                continue                     # (an older development build: A/B only)
-            fn = getattr(L, name)
+            try:
+                fn = getattr(L, name)
+            except AttributeError as e:
+                raise NativeError(f"{LIB_PATH} has no {name}: it was not built from this tree") from e
             fn.argtypes = argt
             fn.restype = rest
         _lib = L

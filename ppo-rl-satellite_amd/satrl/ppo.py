@@ -340,8 +340,6 @@ def rowpass_exchange_check(stream=None, timeout_s=None):
     group (its outputs, hence this update, are invalid), after the library has
     re-armed the exchange state."""
     L = _lib.lib()
-    if _lib.LIB_PATH != _lib._PRODUCT_LIB and not hasattr(L, "satrl_ppo_rowpass_error"):
-        return                               # (an older development build: A/B only)
     e = C.c_int(0)
     t = _dist.dp_timeout_s() if timeout_s is None else float(timeout_s)
     check(L.satrl_ppo_rowpass_error(C.byref(e), t, stream_ptr(stream)), "satrl_ppo_rowpass_error")
@@ -350,14 +348,36 @@ def rowpass_exchange_check(stream=None, timeout_s=None):
                            "together) or an LDS hand-off of the 32-row kernel timed out; the update is invalid")
 
 
+def step_plan(H, mb, net=-1):
+    """satrl_ppo_step_plan (include/satrl_ppo.h): the library's plan of the
+    minibatch step for (H, mb, net) as a _lib.StepPlan -- which kernels run
+    (step, rowpass: _lib.STEP_* / _lib.RP_*), this minibatch's row blocks and
+    splits, whether its rowpass can set the error word, and the capacity of
+    every buffer.  Host arithmetic only, no device call."""
+    plan = _lib.StepPlan()
+    if _lib.lib().satrl_ppo_step_plan(int(H), int(mb), int(net), C.byref(plan)) != 0:
+        raise ValueError(f"satrl_ppo_step_plan: no minibatch step for H {H}, mb {mb}, net {net}")
+    return plan
+
+
+def _update_plans(H, mb, B):
+    """The plans of the minibatches an update of B rows in minibatches of mb
+    steps: the full minibatch min(mb, B) and the ragged tail (none where the
+    library has no step: an empty update, an unsupported width)."""
+    mb = min(int(mb), int(B))
+    plans = []
+    for m in ((mb, int(B) % mb) if mb > 0 else ()):
+        plan = _lib.StepPlan()
+        if m > 0 and _lib.lib().satrl_ppo_step_plan(int(H), m, -1, C.byref(plan)) == 0:
+            plans.append(plan)
+    return plans
+
+
 def uses_column_split(H, mb, B):
     """True when an update of B rows in minibatches of mb may run the
-    column-split short rowpass (H = 256, a full or ragged-tail minibatch of at
-    most 1024 rows; ppo_kernels.hip cs_fits): only such updates need
-    rowpass_exchange_check."""
-    mb = min(int(mb), int(B))
-    tail = int(B) % mb if mb > 0 else 0
-    return H == 256 and mb > 0 and (mb <= 1024 or 0 < tail <= 1024)
+    column-split short rowpass (the plan of its full or ragged-tail minibatch
+    says so: H = 256 up to the kernel's row limit)."""
+    return any(p.rowpass == _lib.RP_CS for p in _update_plans(H, mb, B))
 
 
 def rowpass_sync(mode=None):
@@ -366,10 +386,7 @@ def rowpass_sync(mode=None):
     0 workgroup barriers, 1 per-chunk LDS hand-offs (bitwise the same
     outputs).  Sets the process-wide mode (None: only queries) and returns the
     previous one; a captured graph keeps the form it was captured with."""
-    L = _lib.lib()
-    if _lib.LIB_PATH != _lib._PRODUCT_LIB and not hasattr(L, "satrl_ppo_rowpass_sync"):
-        return 0                             # (an older development build: A/B only)
-    prev = L.satrl_ppo_rowpass_sync(-1 if mode is None else int(mode))
+    prev = _lib.lib().satrl_ppo_rowpass_sync(-1 if mode is None else int(mode))
     if prev < 0:
         raise ValueError(f"rowpass_sync: mode {mode!r} is not 0 or 1")
     return prev
@@ -377,11 +394,10 @@ def rowpass_sync(mode=None):
 
 def uses_handoff(H, mb, B):
     """True when an update of B rows in minibatches of mb runs the hand-off
-    form of the 32-row rowpass (H = 256, minibatches above 1024 rows -- a
-    longer ragged tail has them too -- and rowpass_sync() == 1): its bounded
-    waits report through the same error word, so such updates run
-    rowpass_exchange_check too."""
-    return H == 256 and min(int(mb), int(B)) > 1024 and rowpass_sync() == 1
+    form of the 32-row rowpass (the plan of its full or ragged-tail minibatch
+    says so: H = 256 above the 16-row range while rowpass_sync() == 1).  Its
+    bounded waits report through the column split's error word."""
+    return any(p.rowpass == _lib.RP_WG32_HANDOFF for p in _update_plans(H, mb, B))
 
 
 class FusedMinibatch:
@@ -401,44 +417,43 @@ class FusedMinibatch:
         self.mb = int(mb)
         self.group = int(group)
         self.use_graph = use_graph
-        # dW2 (the fc2 weight gradient dZ2^T H1), hand-written at every width:
-        # H = 64 (configs[1]): the rowpass multiplies each block's dW2 partial
-        # out of LDS itself (satrl_ppo_rowpass_dw2), bitwise the dw2_kernel's
-        # one-chunk splits, so a minibatch step is three launches;
-        # H = 256: the rowpass writes H1 / dZ2 as k-packed bf16 planes and dW2
-        # runs on the split-bf16 MFMA from them (satrl_ppo_rowpass_kx /
-        # satrl_ppo_dw2_kx), for every minibatch size (16-row rowpass blocks up
-        # to 1024 rows: configs[3]'s per-rank minibatch, ragged tails);
-        # H = 128: f32 rows and dw2_kernel (satrl_ppo_dw2)
-        self.fused_dw2 = learner.H == 64
-        self.kx_on = learner.H == 256
-        self.kx_elems = 0
+        # dW2 (the fc2 weight gradient dZ2^T H1), hand-written at every width.
+        # Which step runs, and the size of every buffer, is the library's plan
+        # for this minibatch size (satrl_ppo_step_plan):
+        # STEP_FUSED (H = 64, configs[1]): the rowpass multiplies each block's
+        # dW2 partial out of LDS itself (satrl_ppo_rowpass_dw2), bitwise the
+        # dw2_kernel's one-chunk splits, so a minibatch step is three launches;
+        # STEP_KX (H = 256): the rowpass writes H1 / dZ2 as k-packed bf16 planes
+        # and dW2 runs on the split-bf16 MFMA from them (satrl_ppo_rowpass_kx /
+        # satrl_ppo_dw2_kx_w1), for every minibatch size;
+        # STEP_ROWS (H = 128): f32 rows and dw2_kernel (satrl_ppo_dw2)
+        H, dev = learner.H, learner.device
+        plan = step_plan(H, self.mb)
+        self.step_kind = plan.step
+        self.fused_dw2 = plan.step == _lib.STEP_FUSED
+        self.kx_on = plan.step == _lib.STEP_KX
         # two concurrent per-net chains: measured no faster than one fused chain at
         # H = 256 / 64, mb = 4096 on MI355X (the chains run in lockstep), so off by default
         self.split = bool(split_chains) and learner.pg is None
-        H, dev = learner.H, learner.device
-        nwg, nblk = C.c_int64(), C.c_int64()
-        check(_lib.lib().satrl_ppo_sizes(H, self.mb, C.byref(nwg), C.byref(nblk)), "satrl_ppo_sizes")
-        self.nwg, self.nblk = nwg.value, nblk.value
-        self.S = self.splits(learner.H, self.mb)
+        self.nwg, self.nblk = plan.slab_blocks, plan.norm_blocks
+        self.S = plan.splits
         f32 = dict(dtype=torch.float32, device=dev)
         # f32 H1 / dZ2 rows: satrl_ppo_rowpass (the roofline's rowpass timing,
         # tests) and the H = 128 dW2; the H = 256 step hands them over as planes
-        self.H1 = torch.empty(2 * self.mb * H, **f32)
-        self.dZ2 = torch.empty(2 * self.mb * H, **f32)
+        self.H1 = torch.empty(plan.rows_floats, **f32)
+        self.dZ2 = torch.empty(plan.rows_floats, **f32)
+        self.kx_elems = plan.kx_elems
         if self.kx_on:
-            self.kx_elems = int(_lib.lib().satrl_ppo_kx_elems(H, self.mb))
             self.H1x = torch.empty(self.kx_elems, dtype=torch.int16, device=dev)
             self.dZ2x = torch.empty(self.kx_elems, dtype=torch.int16, device=dev)
-        self.ptail = torch.empty(self.nwg * (6 * H + 12), **f32)
-        self.pw1 = torch.empty(self.nwg * 2 * H * 20, **f32)
-        # sized for the largest split count any minibatch size can produce, so
-        # a ragged tail minibatch whose S exceeds the full minibatch's never
-        # writes past the slabs
-        # (the capacity is fixed here: the launch guard below compares against
-        # it, not against max_splits(), which follows a later change of self.S)
-        self.p2_splits = self.max_splits(H)
-        self.p2 = torch.empty(2 * self.p2_splits * H * H, **f32)
+        self.ptail = torch.empty(plan.ptail_floats, **f32)
+        self.pw1 = torch.empty(plan.pw1_floats, **f32)
+        # sized for the largest split count any minibatch size up to mb can
+        # produce, so a ragged tail minibatch whose S exceeds the full
+        # minibatch's never writes past the slabs (the launch guard below
+        # compares against this capacity)
+        self.p2_splits = plan.max_splits
+        self.p2 = torch.empty(plan.p2_floats, **f32)
         self.nsq = torch.zeros((2, 2 * self.nblk), dtype=torch.float64, device=dev)   # one per chain
         self.idx = torch.zeros((self.group, self.mb), dtype=torch.int64, device=dev)
         # the rows of one group of minibatches, gathered contiguously once per
@@ -498,18 +513,12 @@ class FusedMinibatch:
 
     def dw2_kx_w1(self, mb, S, net, mode, nsq):
         """satrl_ppo_dw2_kx_w1: dw2_kx with the reduce's W1 / tail regions
-        (G, and their norm pairs with mode 3) in the same launch; returns the
-        reduce mode bit that leaves it the W2 region (4), or 0 when the
-        library has no such entry (an older development build: A/B only)."""
-        lib = _lib.lib()
-        if _lib.LIB_PATH != _lib._PRODUCT_LIB and not hasattr(lib, "satrl_ppo_dw2_kx_w1"):
-            self.dw2_kx(mb, S, net)
-            return 0
-        check(lib.satrl_ppo_dw2_kx_w1(self.L.H, int(mb), int(net), int(S), ptr(self.H1x), ptr(self.dZ2x),
-                                      self.H1x.numel(), ptr(self.p2), self.p2.numel(), int(mode), ptr(self.pw1),
-                                      ptr(self.ptail), ptr(self.L.G), None if nsq is None else ptr(nsq), stream_ptr()),
+        (G, and their norm pairs with mode 3) in the same launch; the reduce
+        that follows takes mode bit 4 (the W2 region only)."""
+        check(_lib.lib().satrl_ppo_dw2_kx_w1(self.L.H, int(mb), int(net), int(S), ptr(self.H1x), ptr(self.dZ2x),
+                                             self.H1x.numel(), ptr(self.p2), self.p2.numel(), int(mode), ptr(self.pw1),
+                                             ptr(self.ptail), ptr(self.L.G), ptr(nsq), stream_ptr()),
               "satrl_ppo_dw2_kx_w1")
-        return 4
 
     def rowpass_dw2(self, src, idx, mb=None, net=-1):
         """satrl_ppo_rowpass_dw2 (H = 64): the rowpass with each block's dW2
@@ -553,30 +562,13 @@ class FusedMinibatch:
         return per_row * mb
 
     def max_splits(self, H):
-        """Upper bound of splits(H, mb) over every mb (the p2 capacity)."""
-        if self.fused_dw2:
-            return self.nwg                  # row blocks of the longest minibatch at or below mb
-        if self.kx_on:
-            return max(self.S, 256 // 32)    # (dw2_kx: <= 256 / 32 tiles splits over both nets)
-        return max(self.S, 256 // (2 * (H // 64) ** 2))
+        """Upper bound of splits(H, m) over every m <= mb (the plan's p2 capacity)."""
+        return step_plan(H, self.mb).max_splits
 
     def splits(self, H, mb):
         """split-K ways of the dW2 product for a minibatch of mb rows (both
         nets' count: a one-net chain of split mode uses the same)."""
-        if self.fused_dw2:
-            S = _lib.lib().satrl_ppo_row_blocks(int(H), int(mb))      # one slab per rowpass row block
-            if S < 1:
-                raise _lib.NativeError(f"satrl_ppo_row_blocks({H}, {mb}) failed")
-            return S
-        if self.kx(mb):
-            S = _lib.lib().satrl_ppo_dw2_kx_splits(int(H), int(mb), -1)
-            if S < 1:
-                raise _lib.NativeError(f"satrl_ppo_dw2_kx_splits({H}, {mb}) failed")
-            return S
-        S = _lib.lib().satrl_ppo_dw2_splits(int(H), int(mb))
-        if S < 1:
-            raise _lib.NativeError(f"satrl_ppo_dw2_splits({H}, {mb}) failed")
-        return S
+        return step_plan(H, mb).splits
 
     def _dw2(self, H1, dZ2, mb, S, net):
         """dW2 = dZ2^T @ H1 split-K S ways into the slabs p2 [2][S][H][H] (f32 rows)."""
@@ -596,38 +588,33 @@ class FusedMinibatch:
         nsq = self.nsq[max(net, 0)]
         if events is not None:
             events[0].record()
-        kx = self.kx(mb)
+        kind = self.step_kind
+        H1 = dZ2 = None                                    # (f32 rows: STEP_ROWS only)
         if skip_rowpass:
             n = 2 * mb * H
             H1, dZ2 = self.H1[:n], self.dZ2[:n]
-        elif kx:
+        elif kind == _lib.STEP_KX:
             self.rowpass_kx(src, idx, mb, net)
-            H1 = dZ2 = None
-        elif self.fused_dw2:
+        elif kind == _lib.STEP_FUSED:
             self.rowpass_dw2(src, idx, mb, net)
-            H1 = dZ2 = None
         else:
             H1, dZ2 = self.rowpass(src, idx, mb, net)
         if events is not None:
             events[1].record()
-        # H = 256: the reduce's W1 / tail regions ride in the dW2 launch
-        # (satrl_ppo_dw2_kx_w1), the reduce sums the W2 region (mode bit 4)
-        if L.pg is None:
-            w2 = 0
-            if kx:
-                w2 = self.dw2_kx_w1(mb, S, net, 3, nsq)
-            elif not self.fused_dw2:
-                self._dw2(H1, dZ2, mb, S, net)
-            check(lib.satrl_ppo_reduce(H, mb, net, S, 3 | w2, ptr(self.p2), self.p2.numel(), ptr(self.pw1),
-                                       ptr(self.ptail), ptr(L.G), ptr(nsq), ptr(L.steps), sp), "satrl_ppo_reduce")
-        else:
-            w2 = 0
-            if kx:
-                w2 = self.dw2_kx_w1(mb, S, net, 1, None)
-            elif not self.fused_dw2:
-                self._dw2(H1, dZ2, mb, S, net)
-            check(lib.satrl_ppo_reduce(H, mb, net, S, 1 | w2, ptr(self.p2), self.p2.numel(), ptr(self.pw1),
-                                       ptr(self.ptail), ptr(L.G), None, None, sp), "satrl_ppo_reduce")
+        # the slabs summed into G; alone also the norms and the step counters,
+        # which under data parallelism follow the all-reduce (reduce_dp)
+        dp = L.pg is not None
+        mode = 1 if dp else 3
+        nsq_r, steps_r = (None, None) if dp else (nsq, L.steps)
+        if kind == _lib.STEP_KX:
+            # the reduce's W1 / tail regions ride in the dW2 launch, the reduce sums the W2 region
+            self.dw2_kx_w1(mb, S, net, mode, nsq_r)
+            mode |= 4
+        elif kind == _lib.STEP_ROWS:
+            self._dw2(H1, dZ2, mb, S, net)
+        check(lib.satrl_ppo_reduce(H, mb, net, S, mode, ptr(self.p2), self.p2.numel(), ptr(self.pw1), ptr(self.ptail),
+                                   ptr(L.G), ptr(nsq_r), ptr(steps_r), sp), "satrl_ppo_reduce")
+        if dp:
             # one bucket, both nets: SUM over the ranks, then G /= world and the norms in one launch
             if L.peer is not None and net < 0:
                 L.peer.all_reduce_dp_(H, mb, L.G, nsq, L.steps)              # peer kernel, reduce_dp fused
@@ -961,7 +948,7 @@ class PPOLearner:
                 break
         if self.peer is not None:
             self.peer.check()                # a peer's value never arrived: the update is invalid
-        if uses_column_split(self.H, self.mini_batch_size, B) or uses_handoff(self.H, self.mini_batch_size, B):
+        if any(p.error_word for p in _update_plans(self.H, self.mini_batch_size, B)):
             rowpass_exchange_check()         # (a kernel's bounded wait ran out; bounded by the DP deadline)
         if self.use_lr_decay:
             self.lr_decay(total_steps)

@@ -111,7 +111,7 @@ def test_small_minibatch_gradients(H):
     bar is 8 e32 (the floor below it): 1.6 (H 256, 17 rows gathered, critic
     fc1.bias, err 1.8e-6); where the floor holds, e32 is down to 3e-9 and the
     ratio says little (up to 52, H 64 fc3.bias, err 1.5e-7)."""
-    from satrl.ppo import FusedMinibatch, rowpass_exchange_check
+    from satrl.ppo import FusedMinibatch, rowpass_exchange_check, step_plan
     L, actor, critic = pc.gpu_learner(H)
     P0 = L.P.clone()
     B = 256
@@ -122,6 +122,9 @@ def test_small_minibatch_gradients(H):
     for mb in SMALL_MBS:
         st = FusedMinibatch(L, mb, 1, use_graph=False)
         assert (st.fused_dw2, st.kx_on) == (H == 64, H == 256)
+        plan = step_plan(H, mb)                          # the buffers are the library's plan
+        assert (st.p2.numel(), st.ptail.numel(), st.pw1.numel()) == (plan.p2_floats, plan.ptail_floats, plan.pw1_floats)
+        assert (st.S, st.p2_splits) == (plan.splits, plan.max_splits)
         cases.append((f"mb {mb} gather", st, mb, torch.randperm(B, generator=g)[:mb]))
         cases.append((f"mb {mb} contiguous", st, mb, None))
     for cap in (64, 4096):
