@@ -251,7 +251,45 @@ int satrl_ppo_rowpass_fault_inject(int group, unsigned value, void* stream);
 int satrl_policy_act(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
                      uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act0,
                      float* logp0, float* act1, float* logp1, void* stream);
-/* satrl_policy_eval <- PPO_continuous.evaluate (ppo_continuous.py:168-174) on
+/* satrl_policy_act with an opponent pool: agent pool_agent (0 | 1) acts, per
+ * 32-row block, with a stored parameter set instead of its live one.  pool is
+ * f32 [K][pool_stride], each row a flat parameter set in satrl_ppo_layout's
+ * order; member i32 [ceil(N / 32)] (device) names block b's row:
+ *   m = member[b];  P = 0 <= m < K ? pool + m * pool_stride : the live P0 / P1
+ * Every m outside [0, K) (-1, K, INT_MIN, anything) means the live
+ * parameters; no value of m makes the kernel read outside pool.  The other
+ * agent, the Philox key and counter, env_offset, step and step_base are
+ * exactly satrl_policy_act's, so a block's rows are bit for bit those of
+ * satrl_policy_act called with that block's parameter set.  The granularity
+ * is a block because a workgroup streams one net's weights for its 32 rows.
+ * member and pool are read at every launch: a captured graph follows in-place
+ * changes of either with no recapture.
+ * -1 before any device call (satrl_ppo_last_error says which): every refusal
+ * of satrl_policy_act; a NULL P1, act1 or logp1 (both agents are required);
+ * pool_agent not 0 or 1; a NULL pool or member; K <= 0; pool_stride below
+ * SATRL_PPO_TOTAL of satrl_ppo_layout(H) or not a multiple of 4; pool not
+ * 16-byte aligned.
+ * Span probe: the pooled kernel has no probed instantiation.  While a span
+ * probe is set (satrl_span_probe) a pooled launch runs the product kernel and
+ * adds nothing to the launch log.                                          */
+int satrl_policy_act_pool(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
+                          uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act0,
+                          float* logp0, float* act1, float* logp1, int pool_agent /* 0 | 1 */,
+                          const float* pool /* [K][pool_stride] */, int64_t pool_stride, int K,
+                          const int32_t* member /* [ceil(N/32)], device, read at every launch */, void* stream);
+/* Which stored opponent each 32-env block plays this iteration.  Host only, no
+ * device call.  For global block g = first_block + i, i < n_blocks:
+ *   w = philox4x32_10(counter {lo32(g), hi32(g), lo32(iteration),
+ *       hi32(iteration)}, key of (seed, stream 3))   (streams 0 / 1: the action
+ *       noise, 2: the reset draw)
+ *   u = (w[0] + 0.5) * 2^-32
+ *   member_out[i] = filled == 0 || u < latest_prob ? -1 : (w[1] * filled) >> 32
+ * so an assignment depends on (seed, iteration, g, filled, latest_prob) alone
+ * and not on how the envs are sharded.  -1: a NULL output, n_blocks <= 0,
+ * first_block < 0, filled < 0, latest_prob outside [0, 1] or NaN.          */
+int satrl_opponent_assign(uint64_t seed, uint64_t iteration, int64_t first_block, int64_t n_blocks, int filled,
+                          double latest_prob, int32_t* member_out /* host */);
+/* satrl_policy_eval <-PPO_continuous.evaluate (ppo_continuous.py:168-174) on
  * satrl_policy_act's forward path, block shape and agent interleave; actions
  * only, no log-probs.  Agent a (0: P0, 1: P1) with bit 1 << a of det_mask
  * set acts with the mean, a = max_action*tanh(mean_layer); an agent whose bit

@@ -1700,16 +1700,28 @@ constexpr int kPolRows = 32;   // rows per policy workgroup
 constexpr int kPolNW = 8;      // waves per policy workgroup at H = 256 (16: 61.6 vs 52.3 us per rollout step;
                                // with the wave priority 46.5-47.6 vs 45.1-45.2 us per launch)
 
-template <int H, int NW, int MODE, bool SPAN = false>
-__global__ void __launch_bounds__(NW * 64) policy_kernel(int64_t N, const float* __restrict__ obs,
-                                                     const float* __restrict__ P0, const float* __restrict__ P1,
-                                                     int nagents, float max_action, uint32_t k00, uint32_t k01,
-                                                     uint32_t k10, uint32_t k11, int64_t env_offset, uint64_t step,
-                                                     const uint64_t* __restrict__ step_base,
-                                                     float* __restrict__ act0, float* __restrict__ logp0,
-                                                     float* __restrict__ act1, float* __restrict__ logp1,
-                                                     float* __restrict__ value, int det_mask,
-                                                     unsigned long long* __restrict__ span) {
+// The body of both __global__ forms below.  POOL (MODE 0, two agents): agent
+// `pool_agent`'s workgroups take their parameter base from a stored snapshot,
+//   m = member[block];  P = 0 <= m < K ? pool + m * pool_stride : the live P0 / P1
+// (block = blockIdx.x / nagents; one unsigned compare, so no device value of m
+// addresses anything outside pool).  member[block] is one more dependent load
+// ahead of the weight stream: it is issued first, and a full block's
+// observation float4, which does not depend on it, goes out under it rather
+// than behind the W1 rows that do.  With POOL false every pool argument is
+// dead and the code is policy_kernel's as it was (the
+// resource tables).
+template <int H, int NW, int MODE, bool SPAN, bool POOL>
+__device__ __forceinline__ void policy_body(int64_t N, const float* __restrict__ obs, const float* __restrict__ P0,
+                                            const float* __restrict__ P1, int nagents, float max_action, uint32_t k00,
+                                            uint32_t k01, uint32_t k10, uint32_t k11, int64_t env_offset,
+                                            uint64_t step, const uint64_t* __restrict__ step_base,
+                                            float* __restrict__ act0, float* __restrict__ logp0,
+                                            float* __restrict__ act1, float* __restrict__ logp1,
+                                            float* __restrict__ value, int det_mask,
+                                            unsigned long long* __restrict__ span, const float* __restrict__ pool,
+                                            const int32_t* __restrict__ member, int64_t pool_stride, int K,
+                                            int pool_agent) {
+  static_assert(!POOL || (MODE == 0 && !SPAN), "the pooled form is the product MODE 0 kernel");
   const unsigned long long span_t0 = SPAN ? satrl_span::now() : 0ull;
   constexpr int R = kPolRows, RT = R / 16, CT = H / 16 / NW;
   // Two or more workgroups share a CU, and one finishing its output layer
@@ -1722,8 +1734,18 @@ __global__ void __launch_bounds__(NW * 64) policy_kernel(int64_t N, const float*
   __shared__ MlpSmem<H, NW, R> sm;
   const int agent = MODE != 1 ? (int)(blockIdx.x % nagents) : 0;
   const int64_t r0 = (int64_t)(MODE != 1 ? blockIdx.x / nagents : blockIdx.x) * R;
+  int m = -1;
+  if constexpr (POOL)
+    if (agent == pool_agent) m = member[blockIdx.x / nagents];   // (uniform branch: the other agent's workgroups load nothing more)
   const float* P = agent == 0 ? P0 : P1;
   const int nvalid = (int)(N - r0 < R ? N - r0 : R);
+  float4 pre = make_float4(0.f, 0.f, 0.f, 0.f);                   // (POOL) a full block's float4, in flight under member[block]
+  if constexpr (POOL) {
+    const float* ob = obs + r0 * 18;
+    if (nvalid == R && (reinterpret_cast<uintptr_t>(ob) & 15) == 0 && (int)threadIdx.x < R * 18 / 4)
+      pre = reinterpret_cast<const float4*>(ob)[threadIdx.x];
+    if ((unsigned)m < (unsigned)K) P = pool + (int64_t)m * pool_stride;   // (m stays -1 for the other agent; K > 0)
+  }
   auto gather = [&](int t0, int nt) {
     const float* ob = obs + r0 * 18;
     if (nvalid == R && (reinterpret_cast<uintptr_t>(ob) & 15) == 0) {
@@ -1731,7 +1753,7 @@ __global__ void __launch_bounds__(NW * 64) policy_kernel(int64_t N, const float*
       // every float4 in flight at once (R * 18 / 4 <= one per thread)
       static_assert(R * 18 / 4 <= 4 * 64, "one float4 per thread of the smallest workgroup");
       if (t0 < R * 18 / 4) {
-        const float4 v = reinterpret_cast<const float4*>(ob)[t0];
+        const float4 v = POOL ? pre : reinterpret_cast<const float4*>(ob)[t0];
         const float e4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -1792,6 +1814,43 @@ __global__ void __launch_bounds__(NW * 64) policy_kernel(int64_t N, const float*
     gaussian_act(mu, P[L.ls + d], z[d], max_action, act[i * 3 + d], logp[i * 3 + d]);
   }
   if constexpr (SPAN) satrl_span::exit(span, span_t0);
+}
+
+template <int H, int NW, int MODE, bool SPAN = false>
+__global__ void __launch_bounds__(NW * 64) policy_kernel(int64_t N, const float* __restrict__ obs,
+                                                     const float* __restrict__ P0, const float* __restrict__ P1,
+                                                     int nagents, float max_action, uint32_t k00, uint32_t k01,
+                                                     uint32_t k10, uint32_t k11, int64_t env_offset, uint64_t step,
+                                                     const uint64_t* __restrict__ step_base,
+                                                     float* __restrict__ act0, float* __restrict__ logp0,
+                                                     float* __restrict__ act1, float* __restrict__ logp1,
+                                                     float* __restrict__ value, int det_mask,
+                                                     unsigned long long* __restrict__ span) {
+  policy_body<H, NW, MODE, SPAN, false>(N, obs, P0, P1, nagents, max_action, k00, k01, k10, k11, env_offset, step,
+                                        step_base, act0, logp0, act1, logp1, value, det_mask, span, nullptr, nullptr,
+                                        0, 0, 0);
+}
+
+// The pooled MODE 0 kernel (satrl_policy_act_pool), both agents.  Its first
+// 14 argument dwords (kernarg preload) are what its first loads
+// need: N, obs, pool, member, pool_stride, K, pool_agent, P0 (P1 follows by
+// s_load; packing the stride and K so that it fits too measured no faster,
+// EXPERIMENTS.md).  There is no SPAN instantiation: while a span probe is set
+// a pooled launch runs this kernel and logs nothing.
+template <int H, int NW>
+__global__ void __launch_bounds__(NW * 64) policy_pool_kernel(int64_t N, const float* __restrict__ obs,
+                                                          const float* __restrict__ pool,
+                                                          const int32_t* __restrict__ member, int64_t pool_stride,
+                                                          int K, int pool_agent, const float* __restrict__ P0,
+                                                          const float* __restrict__ P1, float max_action, uint32_t k00,
+                                                          uint32_t k01, uint32_t k10, uint32_t k11,
+                                                          int64_t env_offset, uint64_t step,
+                                                          const uint64_t* __restrict__ step_base,
+                                                          float* __restrict__ act0, float* __restrict__ logp0,
+                                                          float* __restrict__ act1, float* __restrict__ logp1) {
+  policy_body<H, NW, 0, false, true>(N, obs, P0, P1, 2, max_action, k00, k01, k10, k11, env_offset, step, step_base,
+                                     act0, logp0, act1, logp1, nullptr, 0, nullptr, pool, member, pool_stride, K,
+                                     pool_agent);
 }
 
 // ---------------------------------------------------------------------------
@@ -3477,6 +3536,70 @@ int satrl_policy_act(int H, int64_t N, const float* obs, const float* P0, const 
                    P0, P1, nag, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, logp0, act1, logp1,
                    nullptr, 0);
   LAUNCH_CHECK();
+  return 0;
+}
+
+int satrl_policy_act_pool(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
+                          uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act0,
+                          float* logp0, float* act1, float* logp1, int pool_agent, const float* pool,
+                          int64_t pool_stride, int K, const int32_t* member, void* stream) {
+  const char* why = nullptr;
+  if (!valid_h(H) || N <= 0 || !obs || !P0 || !act0 || !logp0)
+    why = "H not 64/128/256, N <= 0, or a NULL obs, P0, act0 or logp0";
+  else if (!P1 || !act1 || !logp1)
+    why = "both agents are required: a NULL P1, act1 or logp1";
+  else if (pool_agent != 0 && pool_agent != 1)
+    why = "pool_agent is 0 or 1";
+  else if (!pool || !member)
+    why = "a NULL pool or member";
+  else if (K <= 0)
+    why = "K <= 0";
+  else if (pool_stride < layout(H).total || pool_stride % 4 != 0)
+    why = "pool_stride below the layout total or not a multiple of 4";
+  else if (reinterpret_cast<uintptr_t>(pool) & 15)
+    why = "pool is not 16-byte aligned";
+  if (why) {
+    g_err = std::string("satrl_policy_act_pool: ") + why;
+    return -1;
+  }
+  uint32_t k00, k01, k10, k11;
+  philox_key(seed, 0, k00, k01);
+  philox_key(seed, 1, k10, k11);
+  const dim3 g((unsigned)(2 * ((N + kPolRows - 1) / kPolRows)));
+  hipStream_t s = (hipStream_t)stream;
+  // (no SPAN form: under a span probe this is the launch, and nothing is logged)
+  if (H == 64)
+    hipLaunchKernelGGL((policy_pool_kernel<64, 4>), g, dim3(256), 0, s, N, obs, pool, member, pool_stride, K,
+                       pool_agent, P0, P1, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, logp0,
+                       act1, logp1);
+  else if (H == 128)
+    hipLaunchKernelGGL((policy_pool_kernel<128, 8>), g, dim3(512), 0, s, N, obs, pool, member, pool_stride, K,
+                       pool_agent, P0, P1, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, logp0,
+                       act1, logp1);
+  else
+    hipLaunchKernelGGL((policy_pool_kernel<256, kPolNW>), g, dim3(kPolNW * 64), 0, s, N, obs, pool, member,
+                       pool_stride, K, pool_agent, P0, P1, max_action, k00, k01, k10, k11, env_offset, step,
+                       step_base, act0, logp0, act1, logp1);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int satrl_opponent_assign(uint64_t seed, uint64_t iteration, int64_t first_block, int64_t n_blocks, int filled,
+                          double latest_prob, int32_t* member_out) {
+  if (!member_out || n_blocks <= 0 || first_block < 0 || filled < 0 || !(latest_prob >= 0.0 && latest_prob <= 1.0)) {
+    g_err = "satrl_opponent_assign: a NULL output, n_blocks <= 0, first_block < 0, filled < 0, or latest_prob "
+            "outside [0, 1]";
+    return -1;
+  }
+  uint32_t k0, k1;
+  philox_key(seed, 3, k0, k1);
+  for (int64_t i = 0; i < n_blocks; ++i) {
+    const uint64_t g = (uint64_t)first_block + (uint64_t)i;
+    uint32_t w[4] = {(uint32_t)g, (uint32_t)(g >> 32), (uint32_t)iteration, (uint32_t)(iteration >> 32)};
+    philox4x32_10(w, k0, k1);
+    const double u = ((double)w[0] + 0.5) * (1.0 / 4294967296.0);
+    member_out[i] = (filled == 0 || u < latest_prob) ? -1 : (int32_t)(((uint64_t)w[1] * (uint64_t)filled) >> 32);
+  }
   return 0;
 }
 

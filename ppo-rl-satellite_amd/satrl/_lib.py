@@ -177,6 +177,9 @@ _SIGS = {
                                   _vp], C.c_int),
     "satrl_policy_act": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_uint64, _i64, C.c_uint64, _vp, _vp, _vp, _vp,
                           _vp, _vp], C.c_int),
+    "satrl_policy_act_pool": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_uint64, _i64, C.c_uint64, _vp, _vp, _vp,
+                               _vp, _vp, C.c_int, _vp, _i64, C.c_int, _vp, _vp], C.c_int),
+    "satrl_opponent_assign": ([C.c_uint64, C.c_uint64, _i64, _i64, C.c_int, C.c_double, _vp], C.c_int),
     "satrl_policy_eval": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_int, C.c_uint64, _i64, C.c_uint64, _vp, _vp,
                            _vp, _vp], C.c_int),
     "satrl_policy_value": ([C.c_int, _i64, _vp, _vp, _vp, _vp], C.c_int),
@@ -223,7 +226,8 @@ def check(rc: int, what: str):
         L = lib()
         msg = (L.satenv_cpu_last_error() if what.startswith("satenv_cpu") else
                L.satenv_last_error() if what.startswith("satenv") else
-               L.satrl_ppo_last_error() if what.startswith(("satrl_ppo", "satrl_peer")) else
+               L.satrl_ppo_last_error() if what.startswith(("satrl_ppo", "satrl_peer", "satrl_policy_act_pool",
+                                                                   "satrl_opponent_assign")) else
                L.satrl_last_error()).decode()
         raise NativeError(f"{what} failed ({rc}): {msg}")
 

@@ -156,12 +156,19 @@ class VecEvaluator:
         self._warm = False
 
     # -- one step -------------------------------------------------------------------------
-    def _step(self, k, det_mask, seed, cap, rec=None):
-        """Step k of a chunk (Philox step k + *step_base); rec: the chunk's stream buffers."""
+    def _step(self, k, det_mask, seed, cap, rec=None, opponent=None):
+        """Step k of a chunk (Philox step k + *step_base); rec: the chunk's stream buffers;
+        opponent: the frozen agent's pool slot that acts in its place (None: its live parameters)."""
         tr = self.trainer
+        P0, P1 = tr.pursuer.P, tr.evader.P
+        if opponent is not None:
+            if tr.flag == 0:
+                P1 = tr.pools["evader"].slot(opponent)
+            else:
+                P0 = tr.pools["pursuer"].slot(opponent)
         if tr.obs_norm:                          # the trainer's current statistics, read only
             _norm.obs_normalize(self.obs_raw, tr.obs_stats, tr.obs_clip, self.policy_input)
-        policy_eval(tr.pursuer.H, self.policy_input, tr.pursuer.P, tr.evader.P, 1.6, det_mask, seed, tr.env_offset, k,
+        policy_eval(tr.pursuer.H, self.policy_input, P0, P1, 1.6, det_mask, seed, tr.env_offset, k,
                     self.pa, self.ea, step_base=self.step_base)
         if rec is not None:
             rec["policy_input"][k].copy_(self.policy_input)
@@ -183,10 +190,11 @@ class VecEvaluator:
                   "reward": ((), torch.float64), "done": ((), torch.uint8)}
         return {k: torch.zeros((steps, N) + s, dtype=dt, device=dev) for k, (s, dt) in shapes.items()}
 
-    def _graph(self, n, flag, det_mask, seed, cap, rec):
-        """The captured chunk of n steps.  The env parameters and the noise
-        seed are launch arguments, so they are part of the key."""
-        key = (flag, n, det_mask, seed, rec is not None, bytes(self.env._p))
+    def _graph(self, n, flag, det_mask, seed, cap, rec, opponent=None):
+        """The captured chunk of n steps.  The env parameters, the noise seed
+        and the opponent slot's pointer are launch arguments, so they are part
+        of the key."""
+        key = (flag, n, det_mask, seed, rec is not None, bytes(self.env._p), opponent)
         if key not in self._graphs:
             if len(self._graphs) >= self.MAX_GRAPHS:
                 self._graphs.clear()
@@ -197,12 +205,12 @@ class VecEvaluator:
                 self._pool = torch.cuda.graph_pool_handle()
             with torch.cuda.graph(g, pool=self._pool, stream=s):
                 for k in range(n):
-                    self._step(k, det_mask, seed, cap, rec)
+                    self._step(k, det_mask, seed, cap, rec, opponent)
             self._graphs[key] = g
         return self._graphs[key]
 
     # -- one evaluation -------------------------------------------------------------------
-    def evaluate(self, deterministic="learner", max_steps=None, states=None, seed=None, record=False):
+    def evaluate(self, deterministic="learner", max_steps=None, states=None, seed=None, record=False, opponent=None):
         tr = self.trainer
         flag = int(tr.flag)
         det_mask = det_mask_of(deterministic, flag)
@@ -252,10 +260,10 @@ class VecEvaluator:
                 n = min(chunk, max_steps - t)
                 self.step_base.fill_(t)
                 if use_graphs:
-                    self._graph(n, flag, det_mask, seed, cap, rec).replay()
+                    self._graph(n, flag, det_mask, seed, cap, rec, opponent).replay()
                 else:
                     for k in range(n):
-                        self._step(k, det_mask, seed, cap, rec)
+                        self._step(k, det_mask, seed, cap, rec, opponent)
                 if record:
                     for name in STREAMS:
                         out[name][t:t + n].copy_(rec[name][:n])

@@ -150,6 +150,28 @@ def policy_act(H, obs, P0, P1, max_action, seed, env_offset, step, act0, logp0, 
                                       ptr(logp0), ptr(act1), ptr(logp1), stream_ptr()), "satrl_policy_act")
 
 
+def policy_act_pool(H, obs, P0, P1, max_action, seed, env_offset, step, act0, logp0, act1, logp1, pool_agent, pool,
+                    member, step_base=None):
+    """policy_act with an opponent pool (satrl_policy_act_pool): agent
+    pool_agent (0 | 1) acts, per 32-row block b, with row member[b] of pool
+    f32 [K, stride] where 0 <= member[b] < K, and with its live parameters for
+    every other value.  pool and member (i32 [ceil(N / 32)], device) are read
+    at every launch."""
+    N = obs.shape[0]
+    _lib.require_cuda(obs, torch.float32, (N, 18), "obs")
+    for t, nm in ((act0, "act0"), (logp0, "logp0"), (act1, "act1"), (logp1, "logp1")):
+        _lib.require_cuda(t, torch.float32, (N, 3), nm)
+    if pool.dim() != 2:
+        raise ValueError(f"pool must be [K, stride], got {tuple(pool.shape)}")
+    K, stride = pool.shape
+    _lib.require_cuda(pool, torch.float32, (K, stride), "pool")
+    _lib.require_cuda(member, torch.int32, ((N + 31) // 32,), "member")
+    check(_lib.lib().satrl_policy_act_pool(int(H), N, ptr(obs), ptr(P0), ptr(P1), float(max_action),
+                                           int(seed) & (2**64 - 1), int(env_offset), int(step), ptr(step_base),
+                                           ptr(act0), ptr(logp0), ptr(act1), ptr(logp1), int(pool_agent), ptr(pool),
+                                           int(stride), int(K), ptr(member), stream_ptr()), "satrl_policy_act_pool")
+
+
 def policy_eval(H, obs, P0, P1, max_action, det_mask, seed, env_offset, step, act0, act1=None, step_base=None):
     """Both agents' actions without log-probs (satrl_policy_eval): agent a
     with bit 1 << a of det_mask set acts with the mean (PPO_continuous.evaluate),

@@ -18,6 +18,8 @@
   without touching any training state, satrl/evaluate.py.  Opt-in
   (diagnostics, target_kl): per-update loss / KL / clip-fraction figures in
   ``VecTrainer.diagnostics`` and the KL early stop of an update's epochs.
+  Opt-in (opponent_pool): the frozen agent of a rollout acts, per 32-env
+  block, with the live opponent or a stored earlier one, satrl/pool.py.
 """
 from __future__ import annotations
 
@@ -28,10 +30,11 @@ import torch
 
 from . import dist as _dist
 from . import norm as _norm
+from . import pool as _pool
 from .buffer import ReplayBuffer, RolloutBuffer
 from .env import VecSatellites
-from .ppo import (PPO_continuous, PPOLearner, gae, gaussian_sample, moments, policy_act, policy_value,
-                  reduce_diagnostics_sums)
+from .ppo import (PPO_continuous, PPOLearner, gae, gaussian_sample, moments, policy_act, policy_act_pool,
+                  policy_value, reduce_diagnostics_sums)
 
 
 class args_param:  # noqa: N801
@@ -46,7 +49,8 @@ class args_param:  # noqa: N801
                  num_envs=1, horizon=None, seed=0, rollout_graph_chunk=64, update_graph_group=64, device=None,
                  surrogate=False, dp_minibatch="global", minibatch_sampler=None, allreduce="rccl",
                  obs_norm=False, reward_scaling=False, obs_clip=10.0, obs_norm_calib_steps=64,
-                 diagnostics=False, diagnostics_rows=None, target_kl=None, reset_spread=None, reset_seed=None):
+                 diagnostics=False, diagnostics_rows=None, target_kl=None, reset_spread=None, reset_seed=None,
+                 opponent_pool=0, opponent_latest_prob=0.5, opponent_snapshot_every=None, opponent_seed=None):
         self.max_train_steps = max_train_steps
         self.evaluate_freq = evaluate_freq
         self.save_freq = save_freq
@@ -134,6 +138,24 @@ class args_param:  # noqa: N801
         # (reset_seed, global env id, the env's episode index); reset_seed None = seed
         self.reset_spread = reset_spread
         self.reset_seed = reset_seed
+        # opponent pool of the vectorised engine's self-play (satrl/pool.py): per agent
+        # a ring of opponent_pool stored parameter sets (0: off, nothing is allocated
+        # and the rollout makes the calls it makes without it).  In every iteration
+        # each 32-env block plays the live opponent with probability
+        # opponent_latest_prob and else a uniformly drawn stored one, keyed by
+        # (opponent_seed, iteration, global block); opponent_seed None = seed.  The
+        # learner is stored at the end of every self_play phase and, with
+        # opponent_snapshot_every = m, after every m-th iteration
+        self.opponent_pool = int(opponent_pool)
+        self.opponent_latest_prob = float(opponent_latest_prob)
+        self.opponent_snapshot_every = None if opponent_snapshot_every is None else int(opponent_snapshot_every)
+        self.opponent_seed = opponent_seed
+        if self.opponent_pool < 0:
+            raise ValueError(f"opponent_pool is the number of stored opponents (0: off), got {opponent_pool}")
+        if not 0.0 <= self.opponent_latest_prob <= 1.0:                  # (NaN fails both comparisons)
+            raise ValueError(f"opponent_latest_prob must be in [0, 1], got {opponent_latest_prob}")
+        if self.opponent_snapshot_every is not None and self.opponent_snapshot_every <= 0:
+            raise ValueError(f"opponent_snapshot_every must be positive or None, got {opponent_snapshot_every}")
         # set by the train_* functions from the env (CPPO_main.py:99-101)
         self.state_dim = 18
         self.action_dim = 3
@@ -361,6 +383,11 @@ class VecTrainer:
             self.ellipse_params = torch.zeros((self.N, 10), dtype=torch.float32, device=self.device)
         if self.obs_norm or self.reward_scaling:
             self._setup_norm(args)
+        self.pools = None
+        self.member = None
+        self.last_assignment = None
+        if int(getattr(args, "opponent_pool", 0)) > 0:
+            self._setup_pools(args)
         rs = getattr(args, "reset_seed", None)
         self.reset_seed = self.seed if rs is None else int(rs)
         self.set_reset_spread(getattr(args, "reset_spread", None))
@@ -399,6 +426,71 @@ class VecTrainer:
         st = self.obs_rms.device_stats()
         self.obs_stats.copy_(torch.from_numpy(st))
         self.obs_pivot.copy_(torch.from_numpy(st[0].copy()))
+
+    # -- opponent pool (satrl/pool.py) ----------------------------------------------------
+    def _setup_pools(self, args):
+        """State of opponent_pool: a pool per agent and the device member
+        tensor, a block of 32 envs (global env id // 32) per entry, so that an
+        assignment does not depend on the sharding: every rank holds whole
+        blocks."""
+        K = int(args.opponent_pool)
+        if self.env_offset % _pool.BLOCK or (self.pg is not None and self.N % _pool.BLOCK):
+            raise ValueError(f"opponent_pool needs env_offset % {_pool.BLOCK} == 0, and under data parallelism "
+                             f"num_envs % {_pool.BLOCK} == 0 (got num_envs={self.N}, env_offset={self.env_offset})")
+        seed = getattr(args, "opponent_seed", None)
+        self.opponent_seed = self.seed if seed is None else int(seed)
+        self.opponent_latest_prob = float(getattr(args, "opponent_latest_prob", 0.5))
+        every = getattr(args, "opponent_snapshot_every", None)
+        self.opponent_snapshot_every = None if every is None else int(every)
+        self.pools = {"pursuer": _pool.OpponentPool(K, self.pursuer.H, self.device, self.opponent_seed),
+                      "evader": _pool.OpponentPool(K, self.evader.H, self.device, self.opponent_seed)}
+        self._n_blocks = (self.N + _pool.BLOCK - 1) // _pool.BLOCK
+        self.member = torch.full((self._n_blocks,), -1, dtype=torch.int32, device=self.device)
+        self.last_assignment = np.full(self._n_blocks, -1, dtype=np.int32)
+
+    @property
+    def frozen_agent(self):
+        """The agent that does not learn under the current Flag."""
+        return "evader" if self.flag == 0 else "pursuer"
+
+    def _assign_opponents(self):
+        """This iteration's member of every local block, over the frozen
+        agent's pool: written into the member tensor in place and
+        stream-ordered (the captured rollout graphs read it on every replay)."""
+        a = self.pools[self.frozen_agent].assign(self.iteration_count, self.env_offset // _pool.BLOCK, self._n_blocks,
+                                                 self.opponent_latest_prob)
+        self.member.copy_(torch.from_numpy(a))
+        self.last_assignment = a
+
+    def snapshot_opponent(self, agent=None):
+        """Store `agent`'s ("pursuer" | "evader"; default: the learner's)
+        current parameters in that agent's pool; returns the slot.  Under data
+        parallelism every rank holds the same parameters and stores them
+        locally."""
+        if self.pools is None:
+            raise ValueError("no opponent pool: build the trainer with args.opponent_pool > 0")
+        if agent is None:
+            agent = "pursuer" if self.learner is self.pursuer else "evader"
+        if agent not in self.pools:
+            raise ValueError("agent is 'pursuer' or 'evader'")
+        L = self.pursuer if agent == "pursuer" else self.evader
+        return self.pools[agent].add(L.P, {"agent": agent, "iteration_count": self.iteration_count,
+                                           "episodes": self.episodes})
+
+    def pool_state(self):
+        """Both pools as CPU tensors with their metas and ring cursors."""
+        if self.pools is None:
+            raise ValueError("no opponent pool: build the trainer with args.opponent_pool > 0")
+        return {k: p.state() for k, p in self.pools.items()}
+
+    def load_pool_state(self, d):
+        """Restore pool_state(), in place: captured rollout graphs stay valid."""
+        if self.pools is None:
+            raise ValueError("no opponent pool: build the trainer with args.opponent_pool > 0")
+        for k, p in self.pools.items():
+            if d.get(k) is None:
+                raise ValueError(f"no {k} pool in this state")
+            p.load_state(d[k])
 
     def set_reset_spread(self, spread, seed=None):
         """The box the env's resets draw their starts from (args_param
@@ -561,8 +653,13 @@ class VecTrainer:
         else:                                    # evader transitions are stored (CPPO_main.py:210)
             pa, plp, ea, elp = self.other_a, self.other_lp, buf.act[t], buf.logp[t]
         # both agents act on s (CPPO_main.py:122-123): one fused launch, pursuer = agent 0
-        policy_act(self.pursuer.H, obs_t, self.pursuer.P, self.evader.P, 1.6, self.seed, self.env_offset, t,
-                   pa, plp, ea, elp, step_base=self.step_base)
+        if self.pools is None:
+            policy_act(self.pursuer.H, obs_t, self.pursuer.P, self.evader.P, 1.6, self.seed, self.env_offset, t,
+                       pa, plp, ea, elp, step_base=self.step_base)
+        else:                                    # the frozen agent acts, per 32-env block, with its member of the pool
+            policy_act_pool(self.pursuer.H, obs_t, self.pursuer.P, self.evader.P, 1.6, self.seed, self.env_offset, t,
+                            pa, plp, ea, elp, 1 - self.flag, self.pools[self.frozen_agent].storage, self.member,
+                            step_base=self.step_base)
         if events is not None:
             events[0].record()
         if env:
@@ -593,13 +690,16 @@ class VecTrainer:
         """Alternating training (the reference's Sign == 0 runs
         train_pursuer_network then train_evader_network, CPPO_main.py:336-338):
         `phases` phases of `iterations_per_phase` iterations, starting with the
-        current Flag.  Returns the per-iteration statistics."""
+        current Flag.  Returns the per-iteration statistics.  With an opponent
+        pool the learner is stored in its pool at the end of every phase."""
         out = []
         for k in range(int(phases)):
             if k:
                 self.set_flag(1 - self.flag)
             for _ in range(int(iterations_per_phase)):
                 out.append((self.flag, self.iteration(timers)))
+            if self.pools is not None:
+                self.snapshot_opponent()
         return out
 
     def _chunk_graph(self, c):
@@ -621,6 +721,8 @@ class VecTrainer:
     def collect(self):
         """T environment steps for all N envs (CPPO_main.py:119-147)."""
         self.step_base.fill_(self.rollout_steps)
+        if self.pools is not None:
+            self._assign_opponents()
         nchunks = (self.T + self.chunk - 1) // self.chunk
         if self.use_graphs:
             if not self._graphs:
@@ -752,7 +854,8 @@ class VecTrainer:
         return out
 
     # -- evaluation (satrl/evaluate.py) -----------------------------------------------------
-    def evaluate(self, num_envs=None, deterministic="learner", max_steps=None, states=None, seed=None, record=False):
+    def evaluate(self, num_envs=None, deterministic="learner", max_steps=None, states=None, seed=None, record=False,
+                 opponent=None):
         """The current policies on a fresh env handle of the evaluator's own
         (`num_envs` envs, default N, this env's parameters): every env's first
         episode, at most max_steps steps (default max_episode_steps), as an
@@ -768,15 +871,32 @@ class VecTrainer:
         evaluator's env draws its starts from the same box under the
         evaluation seed, from episode index 0 on every call: a fixed test set
         of num_envs distinct scenarios (EvalResult.start).  record=True keeps
-        the per-step streams (EvalResult.streams).  No state of the trainer
-        changes.  Under data parallelism each rank evaluates its own envs;
-        results are not reduced across ranks."""
+        the per-step streams (EvalResult.streams).  opponent=k: the frozen
+        agent (the one this Flag does not train) acts with slot k of its
+        opponent pool instead of its live parameters (IndexError for a slot
+        that is not filled, ValueError without a pool).  No state of the
+        trainer changes.  Under data parallelism each rank evaluates its own
+        envs; results are not reduced across ranks."""
         from .evaluate import VecEvaluator
+        if opponent is not None:
+            if self.pools is None:
+                raise ValueError("evaluate(opponent=k) needs an opponent pool (args.opponent_pool > 0)")
+            self.pools[self.frozen_agent].slot(opponent)         # IndexError for a slot that is not filled
+            opponent = int(opponent)
         n = self.N if num_envs is None else int(num_envs)
         if n not in self._evaluators:
             self._evaluators[n] = VecEvaluator(self, n)
         return self._evaluators[n].evaluate(deterministic=deterministic, max_steps=max_steps, states=states, seed=seed,
-                                            record=record)
+                                            record=record, opponent=opponent)
+
+    def evaluate_pool(self, **kw):
+        """evaluate(opponent=k, **kw) against every filled slot of the frozen
+        agent's pool, [(meta, summary)] in slot order: the learner's row of
+        the cross-play table."""
+        if self.pools is None:
+            raise ValueError("evaluate_pool needs an opponent pool (args.opponent_pool > 0)")
+        pool = self.pools[self.frozen_agent]
+        return [(dict(pool.metas[k]), self.evaluate(opponent=k, **kw).summary()) for k in range(pool.filled)]
 
     def iteration(self, timers=None):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
@@ -792,6 +912,9 @@ class VecTrainer:
             # peer aborts the communicator and raises instead of hanging here
             self.learner.comm.wait(_dist.dp_timeout_s())
         stats = self.finish_iteration()
+        if self.pools is not None and self.opponent_snapshot_every and \
+                self.iteration_count % self.opponent_snapshot_every == 0:
+            self.snapshot_opponent()
         if timers is not None:
             torch.cuda.synchronize()
             timers.setdefault("rollout_ms", []).append(ev[0].elapsed_time(ev[1]))
