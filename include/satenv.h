@@ -163,7 +163,16 @@ int satenv_set_reset_dist(satenv_env* h, const satenv_reset_dist* host, void* st
 int satenv_get_reset_dist(const satenv_env* h, satenv_reset_dist* host);
 int satenv_get_episode_index(const satenv_env* h, int32_t* out /* device [N] */, void* stream);
 int satenv_set_episode_index(satenv_env* h, const int32_t* in /* device [N], NULL = zeros */, void* stream);
-/* The same five on the host build's handle (satenv_cpu.h, which includes this
+/* The running return of every env's episode in flight: the 16th f64 plane of
+ * a handle, zeroed by every reset of that env, advanced by every step's
+ * reward and added to stats_out[1] when the episode ends.  Like the episode
+ * index it is not part of get/set_state (SATENV_F64_PLANES stays 15); a
+ * snapshot that is to continue an episode bit for bit needs the pair below
+ * as well.  Stream-ordered device copies, capturable; a null handle (or a
+ * null `out`) returns SATENV_ERR_ARG.                                       */
+int satenv_get_episode_return(const satenv_env* h, double* out /* device [N] */, void* stream);
+int satenv_set_episode_return(satenv_env* h, const double* in /* device [N], NULL = zeros */, void* stream);
+/* The same seven on the host build's handle (satenv_cpu.h, which includes this
  * header; host pointers, synchronous): declared here, next to the struct
  * and the contract they share.                                             */
 struct satenv_cpu_env;
@@ -172,6 +181,8 @@ int satenv_cpu_set_reset_dist(struct satenv_cpu_env* h, const satenv_reset_dist*
 int satenv_cpu_get_reset_dist(const struct satenv_cpu_env* h, satenv_reset_dist* host);
 int satenv_cpu_get_episode_index(const struct satenv_cpu_env* h, int32_t* out, void* stream);
 int satenv_cpu_set_episode_index(struct satenv_cpu_env* h, const int32_t* in, void* stream);
+int satenv_cpu_get_episode_return(const struct satenv_cpu_env* h, double* out, void* stream);
+int satenv_cpu_set_episode_return(struct satenv_cpu_env* h, const double* in, void* stream);
 
 /* Time_window_of_danger_zone(R0_c, V0_c, R0_t, V0_t, Delta_V_c=fuel)
  *   .calculate_number_of_hanger_area()   satellite_function.py:18-99,341-373

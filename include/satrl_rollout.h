@@ -47,6 +47,14 @@ int satrl_gaussian_sample(int64_t N, const float* mean, const float* log_std, fl
 
 /* out f64[2] += (sum x, sum x^2) over x f32 [n]  (out must be zeroed first) */
 int satrl_moments(int64_t n, const float* x, double* out, void* stream);
+/* The same sums, added in a fixed order: equal bits from call to call
+ * (satrl_moments adds its blocks' sums with atomics, in the order the blocks
+ * happen to finish, once n exceeds one block of 256).  scratch: a device
+ * buffer of at least satrl_moments_scratch(n) doubles, overwritten; a smaller
+ * scratch_elems returns -1 before any launch.  Two launches.                 */
+int64_t satrl_moments_scratch(int64_t n);
+int satrl_moments_ordered(int64_t n, const float* x, double* out, double* scratch, int64_t scratch_elems,
+                          void* stream);
 
 /* Running observation normalisation (normalization.py:38-47, frozen statistics).
  * raw, out f32 [N][18], two different buffers; stats f32 [2][18] (mean row,

@@ -86,6 +86,54 @@ __global__ void __launch_bounds__(256) moments_kernel(int64_t n, const float* __
   }
 }
 
+// The same sums with a fixed order of additions (satrl_moments_ordered): the
+// blocks of moments_partial_kernel leave their sums in part[2][blocks], and one
+// block of moments_combine_kernel adds those in block order, so the result
+// does not depend on which block finishes first (the atomics above do).
+__device__ __forceinline__ void block_sum2(double& s, double& s2) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    s += __shfl_xor(s, off, 64);
+    s2 += __shfl_xor(s2, off, 64);
+  }
+  __shared__ double red[2][4];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[0][w] = s; red[1][w] = s2; }
+  __syncthreads();
+  s = 0.0;
+  s2 = 0.0;
+  for (int k = 0; k < (int)(blockDim.x >> 6); ++k) { s += red[0][k]; s2 += red[1][k]; }
+}
+
+__global__ void __launch_bounds__(256) moments_partial_kernel(int64_t n, const float* __restrict__ x,
+                                                              double* __restrict__ part) {
+  double s = 0.0, s2 = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const double v = x[i];
+    s += v;
+    s2 += v * v;
+  }
+  block_sum2(s, s2);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = s;
+    part[gridDim.x + blockIdx.x] = s2;
+  }
+}
+
+__global__ void __launch_bounds__(256) moments_combine_kernel(int blocks, const double* __restrict__ part,
+                                                              double* __restrict__ out) {
+  double s = 0.0, s2 = 0.0;
+  for (int k = threadIdx.x; k < blocks; k += blockDim.x) {
+    s += part[k];
+    s2 += part[blocks + k];
+  }
+  block_sum2(s, s2);
+  if (threadIdx.x == 0) {
+    out[0] += s;
+    out[1] += s2;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Running observation normalisation (normalization.py:38-47 with frozen
 // statistics): out = clamp((raw - mean) * inv_std, +-clip), one subtract and
@@ -382,6 +430,31 @@ int satrl_moments(int64_t n, const float* x, double* out, void* stream) {
   int64_t blocks = (n + 255) / 256;
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(moments_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, x, out);
+  HIP_CHECK_LAUNCH();
+  return 0;
+}
+
+int64_t satrl_moments_scratch(int64_t n) {
+  if (n <= 0) return -1;
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  return 2 * blocks;
+}
+
+int satrl_moments_ordered(int64_t n, const float* x, double* out, double* scratch, int64_t scratch_elems,
+                          void* stream) {
+  if (n <= 0 || !x || !out || !scratch) return -1;
+  const int64_t need = satrl_moments_scratch(n);
+  if (scratch_elems < need) {
+    g_err = "satrl_moments_ordered: scratch holds " + std::to_string(scratch_elems) + " doubles, " +
+            std::to_string(need) + " are needed";
+    return -1;
+  }
+  const int blocks = (int)(need / 2);
+  hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, x,
+                     scratch);
+  HIP_CHECK_LAUNCH();
+  hipLaunchKernelGGL(moments_combine_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, blocks, scratch, out);
   HIP_CHECK_LAUNCH();
   return 0;
 }

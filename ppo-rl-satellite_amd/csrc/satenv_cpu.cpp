@@ -203,6 +203,20 @@ int satenv_cpu_set_episode_index(satenv_cpu_env* h, const int32_t* in, void* /*s
   return SATENV_OK;
 }
 
+int satenv_cpu_get_episode_return(const satenv_cpu_env* h, double* out, void* /*stream*/) {
+  if (!h || !out) return fail(SATENV_ERR_ARG, "satenv_cpu_get_episode_return: null argument");
+  std::memcpy(out, h->f64.data() + (size_t)kPlaneRet * h->n, sizeof(double) * h->n);
+  return SATENV_OK;
+}
+
+int satenv_cpu_set_episode_return(satenv_cpu_env* h, const double* in, void* /*stream*/) {
+  if (!h) return fail(SATENV_ERR_ARG, "satenv_cpu_set_episode_return: null handle");
+  double* dst = h->f64.data() + (size_t)kPlaneRet * h->n;
+  if (in) std::memcpy(dst, in, sizeof(double) * h->n);
+  else std::memset(dst, 0, sizeof(double) * h->n);
+  return SATENV_OK;
+}
+
 int satenv_cpu_danger_zone(int64_t n, const double* states, const double* fuel, const int32_t* fuel_mode,
                            int32_t* count_out, void* /*stream*/) {
   if (n <= 0 || !states || !fuel || !fuel_mode || !count_out)

@@ -930,6 +930,21 @@ int satenv_set_episode_index(satenv_env* h, const int32_t* in, void* stream) {
   return SATENV_OK;
 }
 
+int satenv_get_episode_return(const satenv_env* h, double* out, void* stream) {
+  if (!h || !out) return fail(SATENV_ERR_ARG, "satenv_get_episode_return: null argument");
+  HIP_TRY(hipMemcpyAsync(out, h->f64 + kPlaneRet * h->n, sizeof(double) * h->n, hipMemcpyDeviceToDevice,
+                         (hipStream_t)stream));
+  return SATENV_OK;
+}
+
+int satenv_set_episode_return(satenv_env* h, const double* in, void* stream) {
+  if (!h) return fail(SATENV_ERR_ARG, "satenv_set_episode_return: null handle");
+  double* dst = h->f64 + kPlaneRet * h->n;
+  if (in) HIP_TRY(hipMemcpyAsync(dst, in, sizeof(double) * h->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  else HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * h->n, (hipStream_t)stream));
+  return SATENV_OK;
+}
+
 int satenv_danger_zone(int64_t n, const double* states, const double* fuel, const int32_t* fuel_mode,
                        int32_t* count_out, void* stream) {
   if (n <= 0 || !states || !fuel || !fuel_mode || !count_out) return fail(SATENV_ERR_ARG, "satenv_danger_zone: bad args");

@@ -107,6 +107,10 @@ _SIGS = {
     "satenv_get_reset_dist": ([_vp, C.POINTER(SatenvResetDist)], C.c_int),
     "satenv_get_episode_index": ([_vp, _vp, _vp], C.c_int),
     "satenv_set_episode_index": ([_vp, _vp, _vp], C.c_int),
+    "satenv_get_episode_return": ([_vp, _vp, _vp], C.c_int),
+    "satenv_set_episode_return": ([_vp, _vp, _vp], C.c_int),
+    "satenv_cpu_get_episode_return": ([_vp, _vp, _vp], C.c_int),
+    "satenv_cpu_set_episode_return": ([_vp, _vp, _vp], C.c_int),
     "satenv_cpu_default_reset_dist": ([C.POINTER(SatenvResetDist)], C.c_int),
     "satenv_cpu_set_reset_dist": ([_vp, C.POINTER(SatenvResetDist), _vp], C.c_int),
     "satenv_cpu_get_reset_dist": ([_vp, C.POINTER(SatenvResetDist)], C.c_int),
@@ -129,6 +133,8 @@ _SIGS = {
                                _vp],
                               C.c_int),
     "satrl_moments": ([_i64, _vp, _vp, _vp], C.c_int),
+    "satrl_moments_scratch": ([_i64], _i64),
+    "satrl_moments_ordered": ([_i64, _vp, _vp, _vp, _i64, _vp], C.c_int),
     "satrl_obs_normalize": ([_i64, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp], C.c_int),
     "satrl_return_scan": ([_i64, _i64, _vp, _vp, C.c_double, _vp, _vp, _vp], C.c_int),
     "satrl_episode_record_reset": ([_i64, _vp, _vp, _vp, _vp], C.c_int),

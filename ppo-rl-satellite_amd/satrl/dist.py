@@ -8,6 +8,8 @@ the tensors live on: RCCL over xGMI on the GPUs, gloo in the CPU tests.
 (On the GPUs the per-minibatch gradient all-reduce goes through
 satrl.rccl instead, on the compute stream, so that it is captured in the
 update's hipGraphs.)
+Outside the training step, a checkpoint (satrl.checkpoint) gathers every
+rank's env range and passes three barriers, each under the DP deadline.
 ``pg=None`` means a single process (every function is then local).
 
 Failure path: ``run_or_exit`` runs a multi-rank program and turns any
@@ -64,6 +66,29 @@ def broadcast_object(obj, pg, src: int = 0):
     box = [obj]
     dist.broadcast_object_list(box, src=dist.get_global_rank(pg, src), group=pg)
     return box[0]
+
+
+def all_gather_object(obj, pg):
+    """Every rank's picklable `obj`, in rank order, on every rank."""
+    if pg is None:
+        return [obj]
+    import torch.distributed as dist
+    box = [None] * dist.get_world_size(pg)
+    dist.all_gather_object(box, obj, group=pg)
+    return box
+
+
+def barrier(pg):
+    """Every rank arrives before any leaves, under the DP deadline
+    (dp_timeout_s): a lost peer raises instead of blocking here."""
+    if pg is None:
+        return
+    import datetime
+
+    import torch.distributed as dist
+    work = dist.barrier(group=pg, async_op=True)
+    if not work.wait(datetime.timedelta(seconds=dp_timeout_s())):
+        raise RuntimeError("barrier: a peer did not arrive within the data-parallel deadline")
 
 
 def global_mean_std(local3: torch.Tensor, pg):

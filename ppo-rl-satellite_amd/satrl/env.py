@@ -335,6 +335,46 @@ class VecSatellites:
             self._req(t, torch.int32, (self.num_envs,), "episode index")
         check(self._fn("set_episode_index")(self._h, ptr(t), self._sp()), self._api + "set_episode_index")
 
+    def episode_return(self):
+        """float64 [N]: the running return of every env's episode in flight
+        (the plane get_state leaves out; it feeds stats[1] when the episode ends)."""
+        out = torch.empty(self.num_envs, dtype=torch.float64, device=self.device)
+        check(self._fn("get_episode_return")(self._h, ptr(out), self._sp()), self._api + "get_episode_return")
+        return out
+
+    def set_episode_return(self, t=None):
+        """Set the per-env running returns (float64 [N]; None: zeros)."""
+        if t is not None:
+            self._req(t, torch.float64, (self.num_envs,), "episode return")
+        check(self._fn("set_episode_return")(self._h, ptr(t), self._sp()), self._api + "set_episode_return")
+
+    # -- the whole state (satrl/checkpoint.py) -----------------------------------
+    def full_state(self):
+        """Everything a handle carries from one step to the next, as CPU numpy
+        arrays: the 15 f64 and 3 i32 planes of get_state, the running episode
+        returns, the episode indices and `stats`.  The reset distribution is
+        configuration and is not part of it."""
+        f, i = self.get_state()
+        return {"f64": f.cpu().numpy(), "i32": i.cpu().numpy(), "ep_return": self.episode_return().cpu().numpy(),
+                "episode_index": self.episode_index().cpu().numpy(), "stats": self.stats.cpu().numpy().copy()}
+
+    def load_full_state(self, d):
+        """Restore full_state(), in place and stream-ordered: graphs captured
+        over this handle and over `stats` stay valid."""
+        n = self.num_envs
+        want = {"f64": (np.float64, (SATENV_F64_PLANES, n)), "i32": (np.int32, (SATENV_I32_PLANES, n)),
+                "ep_return": (np.float64, (n,)), "episode_index": (np.int32, (n,)), "stats": (np.float64, (4,))}
+        t = {}
+        for k, (dt, shape) in want.items():
+            a = np.ascontiguousarray(d[k])
+            if a.dtype != dt or a.shape != shape:
+                raise ValueError(f"env state {k!r}: {a.dtype} {a.shape} for {np.dtype(dt)} {shape}")
+            t[k] = torch.from_numpy(a).to(self.device)
+        self.set_state(t["f64"], t["i32"])
+        self.set_episode_return(t["ep_return"])
+        self.set_episode_index(t["episode_index"])
+        self.stats.copy_(t["stats"])
+
     def check_errors(self) -> int:
         st = C.c_int32(0)
         check(self._fn("check")(self._h, C.byref(st)), self._api + "check")

@@ -318,7 +318,12 @@ class UpdateDiagnostics:
 def moments(x, out=None):
     out = torch.zeros(2, dtype=torch.float64, device=x.device) if out is None else out
     x = x.reshape(-1)
-    check(_lib.lib().satrl_moments(x.numel(), ptr(x), ptr(out), stream_ptr()), "satrl_moments")
+    # the fixed-order form: the advantage moments and explained variance of a run and
+    # of its resumed copy are the same bits (satrl_moments' atomics are not)
+    need = int(_lib.lib().satrl_moments_scratch(x.numel()))
+    scratch = torch.empty(max(need, 0), dtype=torch.float64, device=x.device)
+    check(_lib.lib().satrl_moments_ordered(x.numel(), ptr(x), ptr(out), ptr(scratch), scratch.numel(), stream_ptr()),
+          "satrl_moments_ordered")
     return out
 
 
@@ -903,6 +908,29 @@ class PPOLearner:
                   "satrl_ppo_w2x_sync")
         else:
             self.W2T.copy_(w2x_image(self.P[:2 * self.H * self.H], self.H))
+
+    # -- the whole state (satrl/checkpoint.py) --------------------------------------
+    def state(self):
+        """What an update carries to the next, as CPU numpy arrays: the flat
+        parameters P, Adam's moments M and V and step counts (f64 [2]) and the
+        decayed learning rates (f32 [2]).  G and every scratch buffer are
+        rewritten before they are read."""
+        return {"H": self.H, "P": self.P.cpu().numpy(), "M": self.M.cpu().numpy(), "V": self.V.cpu().numpy(),
+                "steps": self.steps.cpu().numpy(), "lr": self.lr.cpu().numpy()}
+
+    def load_state(self, d):
+        """Restore state(), in place: the module parameters (views into P), the
+        captured update graphs and every plan's buffers stay valid; the fc2
+        operand image is refreshed from the new P."""
+        if int(np.asarray(d["H"])) != self.H:
+            raise ValueError(f"a learner state of hidden width {int(np.asarray(d['H']))} for a learner of {self.H}")
+        for k, buf in (("P", self.P), ("M", self.M), ("V", self.V), ("steps", self.steps), ("lr", self.lr)):
+            a = torch.from_numpy(np.ascontiguousarray(d[k]))
+            if a.dtype != buf.dtype or tuple(a.shape) != tuple(buf.shape):
+                raise ValueError(f"learner state {k!r}: {a.dtype} {tuple(a.shape)} for {buf.dtype} "
+                                 f"{tuple(buf.shape)}")
+            buf.copy_(a)
+        self.sync_w2t()
 
     def w2t_f32(self):
         """fc2.weight^T per net [2, H, H] f32 from the operand image."""

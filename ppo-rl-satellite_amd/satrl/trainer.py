@@ -20,6 +20,10 @@
   ``VecTrainer.diagnostics`` and the KL early stop of an update's epochs.
   Opt-in (opponent_pool): the frozen agent of a rollout acts, per 32-env
   block, with the live opponent or a stored earlier one, satrl/pool.py.
+  ``VecTrainer.save_checkpoint`` / ``load_checkpoint`` (and ``train(...,
+  checkpoint_every=k, checkpoint_path=p)``) write and read the whole state
+  between two iterations: a fresh process continues with the bits of the
+  run that never stopped, satrl/checkpoint.py.
 """
 from __future__ import annotations
 
@@ -362,6 +366,8 @@ class VecTrainer:
         self.iteration_count = 0
         self.rollout_steps = 0
         self.episodes = 0.0
+        self._in_iteration = False                           # between collect() and finish_iteration()
+        self._loaded = False                                 # load_state_dict() ran: collect()'s warm-up keeps ep_return
         self.evaluations = []                                # train(evaluate_every=...): (iteration, episodes, summary)
         self._evaluators = {}                                # evaluate(): one cached VecEvaluator per num_envs
         tkl = getattr(args, "target_kl", None)
@@ -686,20 +692,29 @@ class VecTrainer:
         self.learner = self.pursuer if flag == 0 else self.evader
         self._reset_obs()
 
-    def self_play(self, phases, iterations_per_phase, timers=None):
+    def self_play(self, phases, iterations_per_phase, timers=None, checkpoint_every=None, checkpoint_path=None):
         """Alternating training (the reference's Sign == 0 runs
         train_pursuer_network then train_evader_network, CPPO_main.py:336-338):
         `phases` phases of `iterations_per_phase` iterations, starting with the
         current Flag.  Returns the per-iteration statistics.  With an opponent
-        pool the learner is stored in its pool at the end of every phase."""
+        pool the learner is stored in its pool at the end of every phase.
+        checkpoint_path with checkpoint_every=k: save_checkpoint after every
+        k-th iteration of this call and after the last one (a phase's last
+        iteration: after the learner is stored); the saved Flag and
+        iteration_count tell a resumed caller which phases remain."""
         out = []
+        n = int(iterations_per_phase)
         for k in range(int(phases)):
             if k:
                 self.set_flag(1 - self.flag)
-            for _ in range(int(iterations_per_phase)):
+            for j in range(n):
                 out.append((self.flag, self.iteration(timers)))
+                if j + 1 < n:
+                    self._checkpoint_if_due(len(out), checkpoint_every, checkpoint_path)
             if self.pools is not None:
                 self.snapshot_opponent()
+            if n:
+                self._checkpoint_if_due(len(out), checkpoint_every, checkpoint_path, force=k + 1 == int(phases))
         return out
 
     def _chunk_graph(self, c):
@@ -720,6 +735,7 @@ class VecTrainer:
 
     def collect(self):
         """T environment steps for all N envs (CPPO_main.py:119-147)."""
+        self._in_iteration = True
         self.step_base.fill_(self.rollout_steps)
         if self.pools is not None:
             self._assign_opponents()
@@ -727,14 +743,20 @@ class VecTrainer:
         if self.use_graphs:
             if not self._graphs:
                 # eager warm-up of one step so lazy allocations happen before capture
-                # (restores the env state afterwards)
+                # (restores the env state afterwards).  A trainer that loaded a state
+                # runs it in the middle of a run and restores the running episode
+                # returns too; a fresh trainer's first warm-up leaves its reward in
+                # them, as it always has
                 f, i = self.env.get_state()
                 ep = self.env.episode_index()
                 st = self.env.stats.clone()
+                ret = self.env.episode_return() if self._loaded else None
                 self._policy_step(0)
                 self.env.set_state(f, i)
                 self.env.set_episode_index(ep)
                 self.env.stats.copy_(st)
+                if ret is not None:
+                    self.env.set_episode_return(ret)
                 if self.obs_norm:                # the warm-up row is not part of the iteration's sums
                     self.obs_acc.zero_()
                 torch.cuda.synchronize()
@@ -830,7 +852,134 @@ class VecTrainer:
         st = _dist.sum_(self.env.stats, self.pg)
         self.episodes = float(st[0].item())
         self.iteration_count += 1
+        self._in_iteration = False
         return st.cpu().numpy()
+
+    # -- whole state and checkpoints (satrl/checkpoint.py) -------------------
+    def state_dict(self):
+        """Everything the next iteration reads, as a nested dict of CPU numpy
+        arrays, plain scalars and lists of plain records.  Defined between
+        iterations only (after finish_iteration): there the accumulators are
+        zero and the rollout buffer apart from obs[0] is dead; anywhere else
+        this raises.  The surrogate's weights and the reset box are
+        configuration; `member`, `last_assignment` and `ellipse_params` are
+        rewritten by the next rollout."""
+        busy = self._in_iteration
+        if self.obs_norm:
+            busy = busy or self._obs_acc_rows != 0 or bool(self.obs_acc.ne(0).any().item())
+        if self.reward_scaling:
+            busy = busy or bool(self.ret_acc.ne(0).any().item())
+        if busy:
+            raise RuntimeError("a trainer's state is defined between iterations only: call state_dict() / "
+                               "save_checkpoint() after finish_iteration(), not between collect() and it")
+        d = {"flag": self.flag, "iteration_count": int(self.iteration_count), "rollout_steps": int(self.rollout_steps),
+             "episodes": float(self.episodes), "pursuer": self.pursuer.state(), "evader": self.evader.state(),
+             "env": self.env.full_state(), "obs0": self.buf.obs[0].cpu().numpy(),
+             "gen": self.gen.get_state().cpu().numpy().copy(),
+             "diagnostics": [dict(r) for r in self.diagnostics],
+             "evaluations": [[int(it), float(ep), dict(s)] for it, ep, s in self.evaluations]}
+        if self.sampler == "stratified":
+            d["strata_gen"] = {str(s_): g.get_state().cpu().numpy().copy() for s_, g in self.strata_gen.items()}
+        if self.obs_norm:
+            d.update(obs_raw=self.obs_raw.cpu().numpy(), obs_rms=self.obs_rms.state_dict(),
+                     obs_stats=self.obs_stats.cpu().numpy(), obs_pivot=self.obs_pivot.cpu().numpy())
+        if self.reward_scaling:
+            d.update(ret_rms=self.ret_rms.state_dict(), ret_carry=self.ret_carry.cpu().numpy())
+        if self.pools is not None:
+            d["pools"] = {}
+            for k, p in self.pools.items():
+                s = p.state()
+                s["storage"] = s["storage"].numpy()
+                d["pools"][k] = s
+        return d
+
+    def load_state_dict(self, d):
+        """Restore state_dict() in place: captured rollout and update graphs and
+        every tensor a minibatch plan points at stay valid.  Sets the Flag and
+        the learner without restarting the envs; buf.obs[0] is restored as
+        saved, not normalised again.  Without a "gen" entry (a checkpoint read
+        under another sharding) the uniform sampler's generator is seeded as
+        the constructor seeds it."""
+        def scalar(k, typ):
+            return typ(np.asarray(d[k]).item())
+
+        def per_env(k, like):
+            a = torch.from_numpy(np.ascontiguousarray(d[k]))
+            if a.dtype != like.dtype or tuple(a.shape) != tuple(like.shape):
+                raise ValueError(f"state {k!r}: {a.dtype} {tuple(a.shape)} for {like.dtype} {tuple(like.shape)} "
+                                 f"(a state of another env count goes through load_checkpoint)")
+            like.copy_(a)
+
+        flag = scalar("flag", int)
+        if flag not in (0, 1):
+            raise ValueError("Flag 0 (pursuer) or 1 (evader)")
+        for k, on in (("obs_rms", self.obs_norm), ("ret_rms", self.reward_scaling), ("pools", self.pools is not None)):
+            if on != (k in d):
+                raise ValueError(f"this state was saved {'with' if k in d else 'without'} {k}, the trainer runs "
+                                 f"{'with' if on else 'without'} it")
+        self.pursuer.load_state(d["pursuer"])
+        self.evader.load_state(d["evader"])
+        self.env.load_full_state(d["env"])
+        per_env("obs0", self.buf.obs[0])
+        if self.obs_norm:
+            per_env("obs_raw", self.obs_raw)
+            self.obs_rms.load_state_dict(d["obs_rms"])
+            self._write_obs_stats()
+            st = self.obs_rms.device_stats()
+            if not (np.array_equal(st, d["obs_stats"]) and np.array_equal(st[0], d["obs_pivot"])):
+                raise ValueError("the saved device statistics are not those of the saved observation moments")
+            self.obs_acc.zero_()
+            self._obs_acc_rows = 0
+        if self.reward_scaling:
+            self.ret_rms.load_state_dict(d["ret_rms"])
+            per_env("ret_carry", self.ret_carry)
+            self.ret_acc.zero_()
+        if self.pools is not None:
+            for k, p in self.pools.items():
+                s = dict(d["pools"][k])
+                s["K"], s["H"], s["cursor"], s["added"], s["seed"] = (int(np.asarray(s[x]).item()) for x in
+                                                                      ("K", "H", "cursor", "added", "seed"))
+                s["storage"] = torch.from_numpy(np.ascontiguousarray(s["storage"]))
+                p.load_state(s)
+        if "gen" in d:
+            self.gen.set_state(torch.from_numpy(np.ascontiguousarray(d["gen"], dtype=np.uint8)))
+        else:
+            self.gen.manual_seed(self.seed * 1000003 + _dist.rank(self.pg))
+        if self.sampler == "stratified":
+            for s_, g in self.strata_gen.items():
+                g.set_state(torch.from_numpy(np.ascontiguousarray(d["strata_gen"][str(s_)], dtype=np.uint8)))
+        self.flag = flag
+        self.learner = self.pursuer if flag == 0 else self.evader
+        self.iteration_count = scalar("iteration_count", int)
+        self.rollout_steps = scalar("rollout_steps", int)
+        self.episodes = scalar("episodes", float)
+        self.diagnostics = [dict(r) for r in d.get("diagnostics", [])]
+        self.last_diagnostics = self.diagnostics[-1] if self.diagnostics else None
+        self.evaluations = [(int(it), float(ep), dict(s)) for it, ep, s in d.get("evaluations", [])]
+        self._in_iteration = False
+        self._loaded = True
+
+    def save_checkpoint(self, path):
+        """The whole state into the directory `path` (satrl/checkpoint.py): one
+        file per rank and meta.json, written beside `path` and renamed into
+        place once complete.  Under a process group every rank calls this."""
+        from . import checkpoint
+        return checkpoint.save(self, path)
+
+    def load_checkpoint(self, path, global_envs=None):
+        """Continue from save_checkpoint(path), bit for bit where the sharding
+        is the writer's; under another sharding every rank takes its env
+        range out of the writer's files (the uniform sampler's minibatch order
+        is then not the writer's; the stratified one's is).  global_envs:
+        without a process group, the env count of the run this trainer holds a
+        slice of (env_offset; default: this trainer's own N).  Returns the
+        checkpoint's meta."""
+        from . import checkpoint
+        return checkpoint.load(self, path, global_envs)
+
+    def _checkpoint_if_due(self, done, every, path, force=False):
+        if path is not None and (force or (every and done % int(every) == 0)):
+            self.save_checkpoint(path)
 
     @property
     def budget_reached(self):
@@ -839,18 +988,27 @@ class VecTrainer:
         `for epsiode in range(max_train_steps)`), and lr_decay is at 0."""
         return self.episodes >= self.args.max_train_steps
 
-    def train(self, max_iterations=None, timers=None, evaluate_every=None, **eval_kwargs):
+    def train(self, max_iterations=None, timers=None, evaluate_every=None, checkpoint_every=None,
+              checkpoint_path=None, **eval_kwargs):
         """Iterations until the episode budget (or max_iterations) is reached;
         returns the per-iteration statistics.  evaluate_every=k: after every
         k-th iteration, evaluate(**eval_kwargs) and append (iteration_count,
         episodes, summary) to self.evaluations (args.evaluate_freq, which
-        counts the reference's N = 1 steps, stays unread)."""
-        out = []
+        counts the reference's N = 1 steps, stays unread).  checkpoint_path
+        with checkpoint_every=k: save_checkpoint(checkpoint_path) after every
+        k-th iteration and after the last one; the previous checkpoint is
+        replaced only once the new one is complete."""
+        out, saved = [], 0
         while not self.budget_reached and (max_iterations is None or len(out) < max_iterations):
             out.append(self.iteration(timers))
             if evaluate_every and len(out) % int(evaluate_every) == 0:
                 self.evaluations.append((self.iteration_count, self.episodes,
                                          self.evaluate(**eval_kwargs).summary()))
+            if checkpoint_path is not None and checkpoint_every and len(out) % int(checkpoint_every) == 0:
+                self.save_checkpoint(checkpoint_path)
+                saved = len(out)
+        if checkpoint_path is not None and saved != len(out):
+            self.save_checkpoint(checkpoint_path)
         return out
 
     # -- evaluation (satrl/evaluate.py) -----------------------------------------------------
