@@ -353,6 +353,13 @@ int satrl_ppo_group_advance(int64_t* group, void* stream);
  * for torch.tanh in Actor_Gaussian / Critic.forward (ppo_continuous.py:61-134):
  * the hook of its exhaustive accuracy test.                               */
 int satrl_ppo_tanh(int64_t n, const float* x, float* y, void* stream);
+/* Test hook of the wave-uniform arm selection (tanh_f32_n, ppo_kernels.hip):
+ * thread i takes x[8i .. 8i+7], the eight values of an MLP call site, so a
+ * wave is 512 consecutive values; n a multiple of 8.  form 0: the
+ * straight-line two-arm tanh on each value (satrl_ppo_tanh's function),
+ * form 1: the per-wave arm selection on the eight.  The two must agree bit
+ * for bit.                                                                 */
+int satrl_tanh_forms(const float* x, float* y, int64_t n, int form, void* stream);
 
 /* Live launch spans (measurement only; bench.py): while a probe buffer is
  * set, every launch of the rowpass, dW2 (k-packed), reduce, Adam, policy /

@@ -163,16 +163,64 @@ __device__ __forceinline__ void row16_sum_n(float (&v)[NV]) {
 // accurate exp and IEEE division take ~3x that.  Every MLP kernel (rollout
 // policy/value, update rowpass) calls this one function, so logp_old from the
 // rollout still equals the update's recomputation bit for bit.
-__device__ __forceinline__ float tanh_f32(float x) {
-  const float y = fabsf(x), z = x * x;
+__device__ __forceinline__ float tanh_small(float x) {                     // |x| < 0.625
+  const float z = x * x;
   float p = fmaf(-5.70498872745e-3f, z, 2.06390887954e-2f);
   p = fmaf(p, z, -5.37397155531e-2f);
   p = fmaf(p, z, 1.33314422036e-1f);
   p = fmaf(p, z, -3.33332819422e-1f);
-  const float small = fmaf(p * z, x, x);
-  const float e = __builtin_amdgcn_exp2f(y * 2.8853900817779268f);        // e^{2|x|}; inf -> rcp 0 -> 1
+  return fmaf(p * z, x, x);
+}
+__device__ __forceinline__ float tanh_big(float x) {                       // the rest, NaN included
+  const float e = __builtin_amdgcn_exp2f(fabsf(x) * 2.8853900817779268f); // e^{2|x|}; inf -> rcp 0 -> 1
   const float big = fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
-  return y < 0.625f ? small : copysignf(big, x);                          // NaN -> big arm -> NaN
+  return copysignf(big, x);
+}
+__device__ __forceinline__ float tanh_f32(float x) {
+  const float small = tanh_small(x), big = tanh_big(x);
+  return fabsf(x) < 0.625f ? small : big;                                 // NaN -> big arm -> NaN
+}
+// Where the two data-dependent short cuts are compiled in: where they measured
+// faster in the regime that has them (raw-metre observations) and no slower
+// with normalised ones -- the H 256 forward pass (tanh_f32_n on fc1) and the
+// 32-row H 256 rowpass (phase E's zero test).  In the loss head, the
+// column-split kernel and at H 64 / 128 both measured slower, with either kind
+// of observation (EXPERIMENTS.md, "discarded tanh arms").
+template <int H>
+inline constexpr bool kTanhArms = H == 256;
+template <int H, int R>
+inline constexpr bool kZeroSkip = H == 256 && R == 32;
+
+// tanh_f32 of the N values a call site holds, in place, with the arm chosen
+// per wave: the MLP's activations are mostly of one kind over a whole wave --
+// fc1 of raw-metre observations sits at |x| ~ 1e4, where every lane of
+// tanh_f32 still paid for the polynomial it discards.  One compare-OR
+// over the values and one ballot finds a wave with no small value (exp/rcp arm
+// only); a second ballot, off that path, one with small values only
+// (polynomial only); any other wave runs tanh_f32 as it is.  A lane's value
+// goes through the arm tanh_f32 selects for it and the arms are the same
+// instructions (no contraction: -ffp-contract=off), so every result bit is
+// tanh_f32's (GPU test test_tanh_forms_bitwise).
+template <int N>
+__device__ __forceinline__ void tanh_f32_n(float (&v)[N]) {
+  bool any_small = false;
+#pragma unroll
+  for (int q = 0; q < N; ++q) any_small |= fabsf(v[q]) < 0.625f;
+  if (__builtin_amdgcn_ballot_w64(any_small) == 0) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) v[q] = tanh_big(v[q]);
+    return;
+  }
+  bool any_big = false;
+#pragma unroll
+  for (int q = 0; q < N; ++q) any_big |= !(fabsf(v[q]) < 0.625f);
+  if (__builtin_amdgcn_ballot_w64(any_big) == 0) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) v[q] = tanh_small(v[q]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < N; ++q) v[q] = tanh_f32(v[q]);
+  }
 }
 
 // The k mapping of a 32-wide chunk (fc2 / dH1 phases): lane group g holds
@@ -793,11 +841,13 @@ __device__ __forceinline__ void head_consts(float& hls_d, float& hb3_d, float (&
 // rows r0 .. r0 + R of the minibatch (staged: src rows; else src[idx[row]])
 // -> S (the state) and ax (a, logp_old, adv, v_target), thread t0 of nt; the
 // head's constants on the way (HEADC; the hand-off rowpass computes them
-// after the gather's barrier instead, RpHandoff::after_gather)
+// after the gather's barrier instead, RpHandoff::after_gather).  Returns
+// whether every state value this thread put into S is finite (phase E's guard).
 template <int R, int NT, bool HEADC = true, int LDS_S>
-__device__ __forceinline__ void gather_rows(int mb, const float* __restrict__ src, const int64_t* __restrict__ idx,
+__device__ __forceinline__ bool gather_rows(int mb, const float* __restrict__ src, const int64_t* __restrict__ idx,
                                             int r0, int t0, int nt, float (&S)[R][LDS_S], float (&ax)[R][8],
                                             float& hls_d, float& hb3_d, float (&hcs)[3][3], float (&hb3s)[4]) {
+  bool fin = true;
   if (idx == nullptr) {
     // contiguous (staged) rows: one 16-B load per thread covers the block's
     // R x 32 floats, all in flight at once (a loop of dependent scalar
@@ -814,18 +864,35 @@ __device__ __forceinline__ void gather_rows(int mb, const float* __restrict__ sr
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int c = 4 * c4 + e;                                  // s | a, logp_old, adv, v_target | pad
-        if (c < 18) S[r][c] = e4[e];
-        else if (c < 26) ax[r][c - 18] = e4[e];
+        if (c < 18) {
+          S[r][c] = e4[e];
+          fin &= __builtin_isfinite(e4[e]);
+        } else if (c < 26) {
+          ax[r][c - 18] = e4[e];
+        }
       }
     }
   } else {
     for (int q = t0; q < R * 26; q += nt) {
       const int r = q / 26, c = q % 26, row = r0 + r;
       const float v = row < mb ? src[idx[row] * 32 + c] : 0.0f;
-      if (c < 18) S[r][c] = v; else ax[r][c - 18] = v;
+      if (c < 18) {
+        S[r][c] = v;
+        fin &= __builtin_isfinite(v);
+      } else {
+        ax[r][c - 18] = v;
+      }
     }
     if constexpr (HEADC) head_consts<NT>(hls_d, hb3_d, hcs, hb3s);
   }
+  return fin;
+}
+// the guard's publication: word w of nfw says whether wave w gathered a
+// non-finite state value.  Every wave writes its own word before the gather's
+// barrier (nothing to zero first); phase E reads all of them.
+__device__ __forceinline__ void rows_finite_put(unsigned* nfw, bool fin) {
+  const unsigned long long bad = __builtin_amdgcn_ballot_w64(!fin);
+  if ((threadIdx.x & 63) == 0) nfw[threadIdx.x >> 6] = bad != 0 ? 1u : 0u;
 }
 
 // columns 18.. of S: the bias column of W1aug (rows of the minibatch), zero pad
@@ -1065,16 +1132,45 @@ __device__ __forceinline__ void tail(const f4 (&acc)[RT][CT], const float (&w3)[
 // then [dW1 | db1][n][k'] = sum_r dZ1[r][n] S[r][k'] -> pw.
 // acc[rt][t][j] = dZ1[row 16rt+4lg+j][n0+16t+li] is the A operand A[n][r] of
 // the product (k = row, kk = j); B[r][k'] = S[16rt+4lg+kk][16hb + li] from LDS.
-template <int RT, int CT, int LDS_S>
+// Where fc1 is saturated (raw-metre observations: H1 = +-1 exactly) dZ1 is
+// +-0 in every lane, and the MFMAs -- the last thing on the workgroup's path --
+// only add +-0 x S to a +0 accumulator: +0 bits whenever S is finite.  So a
+// wave whose dZ1 values are all +-0 (one OR and one ballot), in a block whose
+// gathered rows are all finite (nfw, rows_finite_put: read only by such a
+// wave), stores +0.0 and skips them; 0 x inf / 0 x NaN keep the MFMA path and
+// its NaNs.
+// SKIP: the kernels that take the short cut (kZeroSkip), nfw their NFW words.
+template <bool SKIP, int NFW, int RT, int CT, int LDS_S>
 __device__ __forceinline__ void phase_e(f4 (&acc)[RT][CT], const float (&h1)[RT][CT][4],
-                                        const float (&S)[16 * RT][LDS_S], float* pw, int n0) {
+                                        const float (&S)[16 * RT][LDS_S], float* pw, int n0,
+                                        const unsigned* nfw) {
   const int l = threadIdx.x & 63, li = l & 15, lg = l >> 4;
+  unsigned nz = 0u;
 #pragma unroll
-  for (int t = 0; t < CT; ++t) {
+  for (int t = 0; t < CT; ++t)
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[rt][t][j] = acc[rt][t][j] * (1.0f - h1[rt][t][j] * h1[rt][t][j]);
+      for (int j = 0; j < 4; ++j) {
+        acc[rt][t][j] = acc[rt][t][j] * (1.0f - h1[rt][t][j] * h1[rt][t][j]);
+        nz |= __float_as_uint(acc[rt][t][j]);
+      }
+  if (SKIP && __builtin_amdgcn_ballot_w64((nz & 0x7fffffffu) != 0u) == 0 &&
+      __builtin_amdgcn_ballot_w64(nfw[l & (NFW - 1)] != 0u) == 0) {
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+#pragma unroll
+      for (int hb = 0; hb < 2; ++hb) {
+        const int kp = 16 * hb + li;
+        if (kp < 20) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) pw[(int64_t)(n0 + 16 * t + 4 * lg + j) * 20 + kp] = 0.0f;
+        }
+      }
+    return;
+  }
+#pragma unroll
+  for (int t = 0; t < CT; ++t) {
 #pragma unroll
     for (int hb = 0; hb < 2; ++hb) {
       f4 d = f4{0.f, 0.f, 0.f, 0.f};
@@ -1214,6 +1310,21 @@ __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* 
     for (int t = 0; t < CT; ++t) acc[rt][t] = f4{0.f, 0.f, 0.f, 0.f};
   mfma_chunk<LDS_S, RT, CT, 4>(&sm.S[li][8 * lg], bw1, acc);
   PHASE_PROBE(10);
+  // fc1 + tanh: a column tile's RT * 4 values per call (tanh_f32_n, where kTanhArms)
+  float hv[CT][RT * 4];
+#pragma unroll
+  for (int t = 0; t < CT; ++t) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) hv[t][4 * rt + j] = acc[rt][t][j];
+    if constexpr (kTanhArms<H>) {
+      tanh_f32_n(hv[t]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < RT * 4; ++q) hv[t][q] = tanh_f32(hv[t][q]);
+    }
+  }
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -1222,7 +1333,7 @@ __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int r = 16 * rt + 4 * lg + j;
-        const float h = tanh_f32(acc[rt][t][j]);                   // fc1 + tanh
+        const float h = hv[t][4 * rt + j];
         h1[rt][t][j] = h;
         if constexpr (!kBf3<H>) sm.h1s[r][n] = h;
       }
@@ -1320,8 +1431,11 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   float h1[RT][CT][4];
   float w3[CT][3];
   unsigned h1w[RT][CT][6];                                         // (split-bf16) the split H1 words
+  constexpr bool ESKIP = kZeroSkip<H, R>;                          // phase E's short cut, and its guard's words
+  __shared__ unsigned nfw[ESKIP ? NW : 1];                         // per wave: gathered a non-finite state value
   auto gather = [&](int t0, int nt) {
-    gather_rows<R, NT, !HANDOFF>(mb, src, idx, r0, t0, nt, S, ax, hls_d, hb3_d, hcs, hb3s);
+    const bool fin = gather_rows<R, NT, !HANDOFF>(mb, src, idx, r0, t0, nt, S, ax, hls_d, hb3_d, hcs, hb3s);
+    if constexpr (ESKIP) rows_finite_put(nfw, fin);
   };
   // how the phases wait for each other (RpBarrier / RpHandoff)
   __shared__ RpFlags flags;
@@ -1387,7 +1501,7 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   PHASE_PROBE(6);
 
   // ---- E: dZ1 = dH1 (1 - H1^2); [dW1 | db1][n][k'] = sum_r dZ1[r][n] S[r][k'] ----
-  phase_e(acc, h1, S, pw1 + (int64_t)rb * 2 * H * 20 + (int64_t)net * H * 20, n0);
+  phase_e<ESKIP, NW>(acc, h1, S, pw1 + (int64_t)rb * 2 * H * 20 + (int64_t)net * H * 20, n0, nfw);
   PHASE_PROBE(7);
 
   // ---- F (FDW2, H <= 128): this block's dW2 partial = dZ2^T H1 over its rows ---
@@ -1675,7 +1789,7 @@ __global__ void __launch_bounds__(kCsWaves * 64) rowpass_cs_kernel(
   mfma_rows3<H, LDP, PS, H, 1, 1, true>(sm.dzp, W2T + (int64_t)net * H * H, n0, acc, &preD);
   PHASE_PROBE(6);
   // ---- E: dZ1, [dW1 | db1] rows of this tile ----------------------------------
-  phase_e(acc, h1, sm.S, pw1 + (int64_t)rb * 2 * H * 20 + (int64_t)net * H * 20, n0);
+  phase_e<false, kCsWaves>(acc, h1, sm.S, pw1 + (int64_t)rb * 2 * H * 20 + (int64_t)net * H * 20, n0, nullptr);
   PHASE_PROBE(7);
   if constexpr (SPAN) satrl_span::exit(span, span_t0);
 }
@@ -2718,6 +2832,26 @@ __global__ void __launch_bounds__(256) tanh_kernel(int64_t n, const float* __res
   if (i < n) y[i] = tanh_f32(x[i]);
 }
 
+// test entry (satrl_tanh_forms): thread i takes x[8i .. 8i+7], a call site's
+// eight values; FORM 0: tanh_f32 on each, FORM 1: tanh_f32_n on the eight
+template <int FORM>
+__global__ void __launch_bounds__(256) tanh_forms_kernel(int64_t n8, const float* __restrict__ x,
+                                                         float* __restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  float v[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) v[q] = x[8 * i + q];
+  if constexpr (FORM == 1) {
+    tanh_f32_n(v);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = tanh_f32(v[q]);
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) y[8 * i + q] = v[q];
+}
+
 // rows per rowpass workgroup for a minibatch of mb rows: kRowsShort at
 // H = 256 up to kShortMb rows (twice the workgroups on the chip; measured
 // faster up to mb 1024, even at 2048, slower at 4096: DESIGN.md §3.4)
@@ -3676,6 +3810,16 @@ int satrl_ppo_diagnostics(int H, int64_t n, const float* src, const int64_t* idx
 int satrl_ppo_tanh(int64_t n, const float* x, float* y, void* stream) {
   if (n <= 0 || n > (int64_t)256 * 0x7FFFFFFF || !x || !y) return -1;
   hipLaunchKernelGGL(tanh_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, x, y);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int satrl_tanh_forms(const float* x, float* y, int64_t n, int form, void* stream) {
+  if (n <= 0 || n % 8 != 0 || n / 8 > (int64_t)256 * 0x7FFFFFFF || !x || !y || form < 0 || form > 1) return -1;
+  const int64_t n8 = n / 8;
+  const dim3 g((unsigned)((n8 + 255) / 256));
+  if (form == 0) hipLaunchKernelGGL(tanh_forms_kernel<0>, g, dim3(256), 0, (hipStream_t)stream, n8, x, y);
+  else hipLaunchKernelGGL(tanh_forms_kernel<1>, g, dim3(256), 0, (hipStream_t)stream, n8, x, y);
   LAUNCH_CHECK();
   return 0;
 }

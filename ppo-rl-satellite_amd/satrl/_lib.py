@@ -195,6 +195,7 @@ _SIGS = {
     "satrl_ppo_stage": ([_i64, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "satrl_ppo_group_advance": ([_vp, _vp], C.c_int),
     "satrl_ppo_tanh": ([_i64, _vp, _vp, _vp], C.c_int),
+    "satrl_tanh_forms": ([_vp, _vp, _i64, C.c_int, _vp], C.c_int),
     "satrl_span_probe": ([_vp, _i64, _vp], C.c_int),
     "satrl_span_probe_launches": ([], _i64),
     "satrl_span_probe_launch": ([_i64, _vp, _vp, _vp], C.c_int),

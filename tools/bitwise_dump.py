@@ -16,6 +16,7 @@ from satrl.ppo import PPOLearner, policy_act, policy_value  # noqa: E402
 from satrl.trainer import args_param  # noqa: E402
 
 H = int(sys.argv[2]) if len(sys.argv) > 2 else 256
+SCALE = float(os.environ.get("OBS_SCALE", "1"))   # 1e5: raw-metre magnitudes (as tools/span_time.py)
 out = {}
 for mb in (4096, 512, 777):
     torch.manual_seed(1)
@@ -25,11 +26,12 @@ for mb in (4096, 512, 777):
     g = torch.Generator(device="cuda").manual_seed(2)
     src = torch.randn((B, 32), device="cuda", generator=g)
     src[:, 21:24] = -1.0 - torch.rand((B, 3), device="cuda", generator=g)
+    src[:, 0:18] *= SCALE
     L.update_packed(src, 0.0, generator=g)
     torch.cuda.synchronize()
     for k in ("P", "M", "V", "G"):
         out[f"{mb}_{k}"] = getattr(L, k).cpu().numpy()
-    obs = torch.randn((16384, 18), device="cuda", generator=g)
+    obs = torch.randn((16384, 18), device="cuda", generator=g) * SCALE
     act = [torch.empty((16384, 3), device="cuda") for _ in range(4)]
     policy_act(H, obs, L.P, L.P, 1.6, 7, 0, 3, *act)
     v = torch.empty(16384, device="cuda")

@@ -47,6 +47,7 @@ L.sync_w2t()
 g = torch.Generator(device="cuda").manual_seed(0)
 src = torch.randn((16 * mb, 32), device="cuda", generator=g)
 src[:, 21:24] = -1.0 - torch.rand((16 * mb, 3), device="cuda", generator=g)
+src[:, 0:18] *= float(os.environ.get("OBS_SCALE", "1"))   # 1e5: raw-metre magnitudes, fc1 saturated (as tools/span_time.py)
 st = L.stepper(mb)
 if os.environ.get("PROBE_CHAIN"):
     # the stamps of the last rowpass of graph-replayed minibatch steps (the

@@ -30,6 +30,7 @@ def main():
     L.sync_w2t()
     g = torch.Generator(device="cuda").manual_seed(0)
     src = torch.randn((rows, 32), device="cuda", generator=g)
+    src[:, 0:18] *= float(os.environ.get("OBS_SCALE", "1"))   # 1e5: raw-metre magnitudes (as tools/span_time.py)
     perm = torch.randperm(rows, device="cuda", generator=g)
     st = L.stepper(mb)
     for k in range(iters):

@@ -4,7 +4,7 @@ time (event-timed graph replays of the update, 16-minibatch groups) and each
 kernel's live launch span (satrl_span_probe: max wave exit - min wave start)
 inside those graphs, for the library SATRL_LIB_PATH selects (default: the
 product build).  Optional: the rollout's policy and env-step spans.
-Usage: [SPAN_REPLAYS=n] python tools/span_time.py H mb[,mb...] [reps] [rollout]
+Usage: [SPAN_REPLAYS=n] [OBS_SCALE=x] python tools/span_time.py H mb[,mb...] [reps] [rollout]
 SPAN_REPLAYS: graph replays (of 16 steps) in the timed window, default 20 (14 ms
 at mb 4096: process-to-process spread 0.7 us); 1500 (a second) resolves 0.2 us."""
 import os
@@ -20,6 +20,9 @@ from satrl.trainer import args_param  # noqa: E402
 
 tag = os.path.basename(os.environ.get("SATRL_LIB_PATH", "product"))
 REPLAYS = int(os.environ.get("SPAN_REPLAYS", "20"))
+# OBS_SCALE: the states' scale.  1 (default): unit-variance states, as under obs_norm; 1e5: raw-metre
+# magnitudes, where fc1 saturates (the bench's regime: tanh_f32_n's exp/rcp arm, phase E's short cut)
+OBS_SCALE = float(os.environ.get("OBS_SCALE", "1"))
 
 
 def step_and_spans(H, mb, n=REPLAYS):
@@ -29,6 +32,7 @@ def step_and_spans(H, mb, n=REPLAYS):
     g = torch.Generator(device="cuda").manual_seed(0)
     src = torch.randn((B, 32), device="cuda", generator=g)
     src[:, 21:24] = -1.0 - torch.rand((B, 3), device="cuda", generator=g)
+    src[:, 0:18] *= OBS_SCALE
     perm = torch.randperm(B, device="cuda", generator=g)
     L.sync_w2t()
     st = FusedMinibatch(L, mb, 16)
