@@ -300,6 +300,52 @@ int satrl_opponent_assign(uint64_t seed, uint64_t iteration, int64_t first_block
 int satrl_policy_eval(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
                       int det_mask, uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base,
                       float* act0, float* act1, void* stream);
+/* Scripted opponents: a linear guidance law in place of a network.  Per env
+ * row, over its 18 RAW observation features s (metres, m/s -- never the
+ * normalised row a learner may see) and action dimension d:
+ *   acc = b[d];  for j = 0..17 ascending: acc = acc + G[d][j] * (double)s[j]
+ *   act[d] = (float) (acc < -m ? -m : acc > m ? m : acc),  m = max_action
+ * every product rounded to f64 and then the sum (no fused multiply-add), the
+ * final conversion round-to-nearest-even; a NaN acc passes the clamp.  The
+ * fixed-horizon intercept and flee laws, coasting and constant thrust are
+ * all of this form (satrl/scripted.py builds G from satenv_stm).           */
+typedef struct satrl_scripted_law {   /* 58 doubles, 464 B */
+  double G[3][18];                    /* row d: weights over the 18 raw observation features */
+  double b[3];
+  double max_action;                  /* > 0 */
+} satrl_scripted_law;
+/* act f32 [N][3] = the law over obs f32 [N][18]; `law` is a DEVICE block, read
+ * at the launch (a captured graph follows in-place changes of it with no
+ * recapture).  -1 before any device call: N <= 0, a NULL obs, law or act.  */
+int satrl_scripted_act(int64_t N, const float* obs, const satrl_scripted_law* law, float* act, void* stream);
+/* The same source through the host compiler on HOST pointers: the same bits,
+ * no device call (the arithmetic's test hook).  -1 as above.               */
+int satrl_scripted_act_host(int64_t N, const float* obs, const satrl_scripted_law* law, float* act);
+/* satrl_policy_act for ONE learning agent against a scripted one, in one
+ * launch.  Agent `agent` (0 pursuer | 1 evader) acts with the flat parameter
+ * set P on obs: its rows of act / logp are bit for bit those satrl_policy_act
+ * writes for that agent (its Philox key stream, the same counter, env_offset,
+ * step, step_base, block shape and forward code).  The other agent's rows,
+ * act_scripted f32 [N][3], are bit for bit satrl_scripted_act(obs_law, law):
+ * a tail of extra workgroups that branch uniformly round the MLP, never touch
+ * P and write no log-prob.  obs_law (the raw observation) may equal obs.
+ * `law` is a device block, read at every launch.
+ * -1 before any device call (satrl_ppo_last_error says which): every refusal
+ * of satrl_policy_act (H not 64/128/256, N <= 0, a NULL obs, P, act or logp);
+ * a NULL obs_law, law or act_scripted; agent not 0 or 1.
+ * Span probe: as the pooled kernel, no probed instantiation; nothing is
+ * logged for these launches.                                               */
+int satrl_policy_act_scripted(int H, int64_t N, const float* obs, const float* obs_law, const float* P,
+                              int agent /* the learner: 0 | 1 */, float max_action, uint64_t seed, int64_t env_offset,
+                              uint64_t step, const uint64_t* step_base, float* act, float* logp,
+                              const satrl_scripted_law* law /* device */, float* act_scripted, void* stream);
+/* The same for satrl_policy_eval, actions only: det = 1, agent `agent` acts
+ * with its mean; det = 0, it samples, bit for bit as in satrl_policy_eval.
+ * -1 as above (no logp), and for det not 0 or 1.                            */
+int satrl_policy_eval_scripted(int H, int64_t N, const float* obs, const float* obs_law, const float* P,
+                               int agent /* 0 | 1 */, float max_action, int det /* 0 | 1 */, uint64_t seed,
+                               int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act,
+                               const satrl_scripted_law* law /* device */, float* act_scripted, void* stream);
 /* critic value v f32 [N] of the flat parameters P (net 1) <- self.critic(s),
  * ppo_continuous.py:200-201                                               */
 int satrl_policy_value(int H, int64_t N, const float* obs, const float* P, float* v_out, void* stream);

@@ -28,6 +28,7 @@
 #include "span_probe.h"
 #include "satrl_ppo.h"
 #include "satrl_peer.h"
+#include "scripted_device.h"
 
 namespace {
 
@@ -1968,6 +1969,54 @@ __global__ void __launch_bounds__(NW * 64) policy_pool_kernel(int64_t N, const f
 }
 
 // ---------------------------------------------------------------------------
+// Scripted opponents: one agent of the rollout acts with a
+// linear guidance law (scripted_device.h) instead of a network.
+//   scripted_kernel          the law alone, a lane per env row
+//   policy_scripted_kernel   the learner's MODE 0 / MODE 2 forward in
+//                            policy_kernel's one-agent grid (workgroups
+//                            0 .. nblk-1, policy_body as policy_kernel
+//                            instantiates it) and, behind them, a tail of
+//                            workgroups that branch uniformly round the MLP
+//                            and evaluate the law, a lane per row: no
+//                            parameter, no LDS, no log-prob.
+// The learner's Philox key arrives as (k0, k1): the host passes the key
+// stream of the learner's agent id, so an evader learner draws agent 1's
+// noise although its workgroups run as policy_body's agent 0.  The first 14
+// argument dwords (kernarg preload) are N, obs, P, obs_law, law, act_scripted,
+// nblk and max_action: what either branch's first loads need.
+// ---------------------------------------------------------------------------
+constexpr int kScriptedBlock = 256;   // rows per workgroup of scripted_kernel
+
+__global__ void __launch_bounds__(kScriptedBlock) scripted_kernel(int64_t N, const float* __restrict__ obs,
+                                                                  const satrl_scripted_law* __restrict__ law,
+                                                                  float* __restrict__ act) {
+  const int64_t i = (int64_t)blockIdx.x * kScriptedBlock + threadIdx.x;
+  if (i < N) satrl_scripted::law_row(law, obs + i * 18, act + i * 3);
+}
+
+template <int H, int NW, int MODE>
+__global__ void __launch_bounds__(NW * 64) policy_scripted_kernel(int64_t N, const float* __restrict__ obs,
+                                                              const float* __restrict__ P,
+                                                              const float* __restrict__ obs_law,
+                                                              const satrl_scripted_law* __restrict__ law,
+                                                              float* __restrict__ act_scripted, int nblk,
+                                                              float max_action, uint32_t k0, uint32_t k1,
+                                                              int64_t env_offset, uint64_t step,
+                                                              const uint64_t* __restrict__ step_base,
+                                                              float* __restrict__ act, float* __restrict__ logp,
+                                                              int det) {
+  static_assert(MODE == 0 || MODE == 2, "the act and the eval form");
+  if ((int)blockIdx.x >= nblk) {                                  // (uniform: the scripted agent's workgroups)
+    const int64_t i = (int64_t)((int)blockIdx.x - nblk) * (NW * 64) + threadIdx.x;
+    if (i < N) satrl_scripted::law_row(law, obs_law + i * 18, act_scripted + i * 3);
+    return;
+  }
+  policy_body<H, NW, MODE, false, false>(N, obs, P, nullptr, 1, max_action, k0, k1, 0u, 0u, env_offset, step,
+                                         step_base, act, logp, nullptr, nullptr, nullptr, det, nullptr, nullptr,
+                                         nullptr, 0, 0, 0);
+}
+
+// ---------------------------------------------------------------------------
 // Update diagnostics (satrl_ppo_diagnostics): the forward pass of both nets
 // over rows src[idx[r]] of the packed table and, per (32-row block, net)
 // workgroup, f64 partial sums of what the loss head sees -- the policy
@@ -2935,6 +2984,50 @@ void launch_policy(int H, int kind, dim3 g, void* stream, A... args) {
     launch_span(policy_kernel<256, kPolNW, MODE, true>, policy_kernel<256, kPolNW, MODE>, sp, g, dim3(nw * 64), stream,
                 args...);
 }
+// the launch of both fused forms (MODE 0: act + logp, MODE 2: actions only)
+template <int MODE>
+int launch_policy_scripted(const char* who, int H, int64_t N, const float* obs, const float* obs_law,
+                                  const float* P, int agent, float max_action, int det, uint64_t seed,
+                                  int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act,
+                                  float* logp, const satrl_scripted_law* law, float* act_scripted, void* stream) {
+  const char* why = nullptr;
+  if (!valid_h(H) || N <= 0 || !obs || !P || !act || (MODE == 0 && !logp))
+    why = MODE == 0 ? "H not 64/128/256, N <= 0, or a NULL obs, P, act or logp"
+                    : "H not 64/128/256, N <= 0, or a NULL obs, P or act";
+  else if (!obs_law || !law || !act_scripted)
+    why = "a NULL obs_law, law or act_scripted";
+  else if (agent != 0 && agent != 1)
+    why = "agent is 0 or 1";
+  else if (det != 0 && det != 1)
+    why = "det is 0 or 1";
+  if (why) {
+    g_err = std::string(who) + ": " + why;
+    return -1;
+  }
+  uint32_t k0, k1;
+  philox_key(seed, (uint32_t)agent, k0, k1);                       // the learner's own key stream
+  const int nw = H == 64 ? 4 : H == 128 ? 8 : kPolNW;
+  const int64_t nblk = (N + kPolRows - 1) / kPolRows;
+  const int64_t ntail = (N + nw * 64 - 1) / (nw * 64);
+  if (nblk + ntail > 0x7FFFFFFF) {
+    g_err = std::string(who) + ": N is too large for one grid";
+    return -1;
+  }
+  const dim3 g((unsigned)(nblk + ntail));
+  hipStream_t s = (hipStream_t)stream;
+  if (H == 64)
+    hipLaunchKernelGGL((policy_scripted_kernel<64, 4, MODE>), g, dim3(256), 0, s, N, obs, P, obs_law, law,
+                       act_scripted, (int)nblk, max_action, k0, k1, env_offset, step, step_base, act, logp, det);
+  else if (H == 128)
+    hipLaunchKernelGGL((policy_scripted_kernel<128, 8, MODE>), g, dim3(512), 0, s, N, obs, P, obs_law, law,
+                       act_scripted, (int)nblk, max_action, k0, k1, env_offset, step, step_base, act, logp, det);
+  else
+    hipLaunchKernelGGL((policy_scripted_kernel<256, kPolNW, MODE>), g, dim3(kPolNW * 64), 0, s, N, obs, P, obs_law,
+                       law, act_scripted, (int)nblk, max_action, k0, k1, env_offset, step, step_base, act, logp, det);
+  LAUNCH_CHECK();
+  return 0;
+}
+
 // the two instantiations of a rowpass_kernel, {probed, plain}
 template <int H, int NW, int R, bool FDW2, bool KX, bool HANDOFF = false>
 auto rowpass_k() {
@@ -3752,6 +3845,33 @@ int satrl_policy_eval(int H, int64_t N, const float* obs, const float* P0, const
                    nullptr, nullptr, det_mask);
   LAUNCH_CHECK();
   return 0;
+}
+
+int satrl_scripted_act(int64_t N, const float* obs, const satrl_scripted_law* law, float* act, void* stream) {
+  if (N <= 0 || !obs || !law || !act) {
+    g_err = "satrl_scripted_act: N <= 0, or a NULL obs, law or act";
+    return -1;
+  }
+  hipLaunchKernelGGL(scripted_kernel, dim3((unsigned)((N + kScriptedBlock - 1) / kScriptedBlock)),
+                     dim3(kScriptedBlock), 0, (hipStream_t)stream, N, obs, law, act);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int satrl_policy_act_scripted(int H, int64_t N, const float* obs, const float* obs_law, const float* P, int agent,
+                              float max_action, uint64_t seed, int64_t env_offset, uint64_t step,
+                              const uint64_t* step_base, float* act, float* logp, const satrl_scripted_law* law,
+                              float* act_scripted, void* stream) {
+  return launch_policy_scripted<0>("satrl_policy_act_scripted", H, N, obs, obs_law, P, agent, max_action, 0, seed,
+                                   env_offset, step, step_base, act, logp, law, act_scripted, stream);
+}
+
+int satrl_policy_eval_scripted(int H, int64_t N, const float* obs, const float* obs_law, const float* P, int agent,
+                               float max_action, int det, uint64_t seed, int64_t env_offset, uint64_t step,
+                               const uint64_t* step_base, float* act, const satrl_scripted_law* law,
+                               float* act_scripted, void* stream) {
+  return launch_policy_scripted<2>("satrl_policy_eval_scripted", H, N, obs, obs_law, P, agent, max_action, det, seed,
+                                   env_offset, step, step_base, act, nullptr, law, act_scripted, stream);
 }
 
 int satrl_policy_value(int H, int64_t N, const float* obs, const float* P, float* v_out, void* stream) {

@@ -188,6 +188,12 @@ _SIGS = {
     "satrl_opponent_assign": ([C.c_uint64, C.c_uint64, _i64, _i64, C.c_int, C.c_double, _vp], C.c_int),
     "satrl_policy_eval": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_int, C.c_uint64, _i64, C.c_uint64, _vp, _vp,
                            _vp, _vp], C.c_int),
+    "satrl_scripted_act": ([_i64, _vp, _vp, _vp, _vp], C.c_int),
+    "satrl_scripted_act_host": ([_i64, _vp, _vp, _vp], C.c_int),
+    "satrl_policy_act_scripted": ([C.c_int, _i64, _vp, _vp, _vp, C.c_int, C.c_float, C.c_uint64, _i64, C.c_uint64, _vp,
+                                   _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "satrl_policy_eval_scripted": ([C.c_int, _i64, _vp, _vp, _vp, C.c_int, C.c_float, C.c_int, C.c_uint64, _i64,
+                                    C.c_uint64, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "satrl_policy_value": ([C.c_int, _i64, _vp, _vp, _vp, _vp], C.c_int),
     "satrl_ppo_diagnostics_scratch": ([_i64], _i64),
     "satrl_ppo_diagnostics": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _i64, _vp, _vp],
@@ -234,7 +240,9 @@ def check(rc: int, what: str):
         msg = (L.satenv_cpu_last_error() if what.startswith("satenv_cpu") else
                L.satenv_last_error() if what.startswith("satenv") else
                L.satrl_ppo_last_error() if what.startswith(("satrl_ppo", "satrl_peer", "satrl_policy_act_pool",
-                                                                   "satrl_opponent_assign")) else
+                                                                   "satrl_opponent_assign", "satrl_scripted_act",
+                                                                   "satrl_policy_act_scripted",
+                                                                   "satrl_policy_eval_scripted")) else
                L.satrl_last_error()).decode()
         raise NativeError(f"{what} failed ({rc}): {msg}")
 

@@ -29,7 +29,8 @@ import torch
 
 from . import norm as _norm
 from .env import VecSatellites, _typed
-from .ppo import REC_F64, REC_I32, episode_record, episode_record_reset, policy_eval
+from .ppo import REC_F64, REC_I32, episode_record, episode_record_reset, policy_eval, policy_eval_scripted
+from .scripted import ScriptedLaw
 
 # the default noise seed of an evaluation is args.seed ^ EVAL_SEED_XOR: another
 # Philox key than the training rollout's, the same one on every call
@@ -152,6 +153,7 @@ class VecEvaluator:
         self._no_mask = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._chunk_streams = None
         self._graphs = {}
+        self._laws = {}
         self._pool = None
         self._warm = False
 
@@ -161,6 +163,15 @@ class VecEvaluator:
         opponent: the frozen agent's pool slot that acts in its place (None: its live parameters)."""
         tr = self.trainer
         P0, P1 = tr.pursuer.P, tr.evader.P
+        if isinstance(opponent, ScriptedLaw):    # the frozen agent's law on the raw row, the learner's MLP alone
+            if tr.obs_norm:
+                _norm.obs_normalize(self.obs_raw, tr.obs_stats, tr.obs_clip, self.policy_input)
+            learner_act, law_act = (self.pa, self.ea) if tr.flag == 0 else (self.ea, self.pa)
+            policy_eval_scripted(tr.learner.H, self.policy_input, self.obs_raw, tr.learner.P, tr.flag, 1.6,
+                                 (det_mask >> tr.flag) & 1, seed, tr.env_offset, k, learner_act, opponent, law_act,
+                                 step_base=self.step_base)
+            self._after_policy(k, cap, rec)
+            return
         if opponent is not None:
             if tr.flag == 0:
                 P1 = tr.pools["evader"].slot(opponent)
@@ -170,6 +181,10 @@ class VecEvaluator:
             _norm.obs_normalize(self.obs_raw, tr.obs_stats, tr.obs_clip, self.policy_input)
         policy_eval(tr.pursuer.H, self.policy_input, P0, P1, 1.6, det_mask, seed, tr.env_offset, k,
                     self.pa, self.ea, step_base=self.step_base)
+        self._after_policy(k, cap, rec)
+
+    def _after_policy(self, k, cap, rec):
+        """The rest of step k once both actions are in pa / ea: env step and record."""
         if rec is not None:
             rec["policy_input"][k].copy_(self.policy_input)
             rec["pursuer_action"][k].copy_(self.pa)
@@ -192,12 +207,17 @@ class VecEvaluator:
 
     def _graph(self, n, flag, det_mask, seed, cap, rec, opponent=None):
         """The captured chunk of n steps.  The env parameters, the noise seed
-        and the opponent slot's pointer are launch arguments, so they are part
-        of the key."""
-        key = (flag, n, det_mask, seed, rec is not None, bytes(self.env._p), opponent)
+        and the opponent slot's pointer (a scripted law's block: the law's
+        identity, not its values, which the kernel reads at every launch) are
+        launch arguments, so they are part of the key."""
+        okey = ("law", id(opponent)) if isinstance(opponent, ScriptedLaw) else opponent
+        key = (flag, n, det_mask, seed, rec is not None, bytes(self.env._p), okey)
         if key not in self._graphs:
             if len(self._graphs) >= self.MAX_GRAPHS:
                 self._graphs.clear()
+                self._laws.clear()
+            if isinstance(opponent, ScriptedLaw):
+                self._laws[id(opponent)] = opponent          # keeps the block (and the id) alive with its graphs
             s = torch.cuda.Stream(device=self.device)
             s.wait_stream(torch.cuda.current_stream())
             g = torch.cuda.CUDAGraph()

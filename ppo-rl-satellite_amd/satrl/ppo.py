@@ -172,6 +172,52 @@ def policy_act_pool(H, obs, P0, P1, max_action, seed, env_offset, step, act0, lo
                                            int(stride), int(K), ptr(member), stream_ptr()), "satrl_policy_act_pool")
 
 
+def _law_block(law, device):
+    """The device block (f64 [58]) of a satrl.scripted.ScriptedLaw, or the tensor itself."""
+    blk = law.block(device) if hasattr(law, "block") else law
+    return _lib.require_cuda(blk, torch.float64, (58,), "law")
+
+
+def policy_act_scripted(H, obs, obs_law, P, agent, max_action, seed, env_offset, step, act, logp, law, act_scripted,
+                        step_base=None):
+    """policy_act for one learning agent against a scripted one
+    (satrl_policy_act_scripted): agent `agent` (0 | 1) acts with P on obs, bit
+    for bit its rows of policy_act; the other agent's actions act_scripted are
+    `law` (a ScriptedLaw or its device block, read at every launch) over the
+    raw observation obs_law, which may be obs."""
+    N = obs.shape[0]
+    _lib.require_cuda(obs, torch.float32, (N, 18), "obs")
+    _lib.require_cuda(obs_law, torch.float32, (N, 18), "obs_law")
+    for t, nm in ((act, "act"), (logp, "logp"), (act_scripted, "act_scripted")):
+        _lib.require_cuda(t, torch.float32, (N, 3), nm)
+    if agent not in (0, 1):
+        raise ValueError(f"agent is 0 (pursuer) or 1 (evader), got {agent!r}")
+    check(_lib.lib().satrl_policy_act_scripted(int(H), N, ptr(obs), ptr(obs_law), ptr(P), int(agent),
+                                               float(max_action), int(seed) & (2**64 - 1), int(env_offset), int(step),
+                                               ptr(step_base), ptr(act), ptr(logp), ptr(_law_block(law, obs.device)),
+                                               ptr(act_scripted), stream_ptr()), "satrl_policy_act_scripted")
+
+
+def policy_eval_scripted(H, obs, obs_law, P, agent, max_action, det, seed, env_offset, step, act, law, act_scripted,
+                         step_base=None):
+    """policy_eval for one network agent against a scripted one
+    (satrl_policy_eval_scripted): det 1, agent `agent` acts with its mean;
+    det 0, with policy_act's sample."""
+    N = obs.shape[0]
+    _lib.require_cuda(obs, torch.float32, (N, 18), "obs")
+    _lib.require_cuda(obs_law, torch.float32, (N, 18), "obs_law")
+    for t, nm in ((act, "act"), (act_scripted, "act_scripted")):
+        _lib.require_cuda(t, torch.float32, (N, 3), nm)
+    if agent not in (0, 1):
+        raise ValueError(f"agent is 0 (pursuer) or 1 (evader), got {agent!r}")
+    if det not in (0, 1):
+        raise ValueError(f"det is 0 or 1, got {det!r}")
+    check(_lib.lib().satrl_policy_eval_scripted(int(H), N, ptr(obs), ptr(obs_law), ptr(P), int(agent),
+                                                float(max_action), int(det), int(seed) & (2**64 - 1), int(env_offset),
+                                                int(step), ptr(step_base), ptr(act), ptr(_law_block(law, obs.device)),
+                                                ptr(act_scripted), stream_ptr()), "satrl_policy_eval_scripted")
+
+
 def policy_eval(H, obs, P0, P1, max_action, det_mask, seed, env_offset, step, act0, act1=None, step_base=None):
     """Both agents' actions without log-probs (satrl_policy_eval): agent a
     with bit 1 << a of det_mask set acts with the mean (PPO_continuous.evaluate),

@@ -23,7 +23,9 @@
   ``VecTrainer.save_checkpoint`` / ``load_checkpoint`` (and ``train(...,
   checkpoint_every=k, checkpoint_path=p)``) write and read the whole state
   between two iterations: a fresh process continues with the bits of the
-  run that never stopped, satrl/checkpoint.py.
+  run that never stopped, satrl/checkpoint.py.  Opt-in (scripted_opponent):
+  an agent acts, whenever it is the frozen one, with a linear guidance law
+  instead of its network, satrl/scripted.py.
 """
 from __future__ import annotations
 
@@ -35,10 +37,11 @@ import torch
 from . import dist as _dist
 from . import norm as _norm
 from . import pool as _pool
+from . import scripted as _scripted
 from .buffer import ReplayBuffer, RolloutBuffer
 from .env import VecSatellites
 from .ppo import (PPO_continuous, PPOLearner, gae, gaussian_sample, moments, policy_act, policy_act_pool,
-                  policy_value, reduce_diagnostics_sums)
+                  policy_act_scripted, policy_value, reduce_diagnostics_sums)
 
 
 class args_param:  # noqa: N801
@@ -54,7 +57,8 @@ class args_param:  # noqa: N801
                  surrogate=False, dp_minibatch="global", minibatch_sampler=None, allreduce="rccl",
                  obs_norm=False, reward_scaling=False, obs_clip=10.0, obs_norm_calib_steps=64,
                  diagnostics=False, diagnostics_rows=None, target_kl=None, reset_spread=None, reset_seed=None,
-                 opponent_pool=0, opponent_latest_prob=0.5, opponent_snapshot_every=None, opponent_seed=None):
+                 opponent_pool=0, opponent_latest_prob=0.5, opponent_snapshot_every=None, opponent_seed=None,
+                 scripted_opponent=None):
         self.max_train_steps = max_train_steps
         self.evaluate_freq = evaluate_freq
         self.save_freq = save_freq
@@ -160,6 +164,16 @@ class args_param:  # noqa: N801
             raise ValueError(f"opponent_latest_prob must be in [0, 1], got {opponent_latest_prob}")
         if self.opponent_snapshot_every is not None and self.opponent_snapshot_every <= 0:
             raise ValueError(f"opponent_snapshot_every must be positive or None, got {opponent_snapshot_every}")
+        # scripted opponents of the vectorised engine (satrl/scripted.py): None, a mapping
+        # {"evader": law, "pursuer": law} with either key optional, or a builder's name
+        # ("coast", "intercept", "evade") / a ScriptedLaw as shorthand for {"evader": ...}.
+        # An agent's law acts whenever that agent is the frozen one, on the raw
+        # observation; its network, parameters and Adam state stay live, and set_flag /
+        # self_play make it the learner as before
+        self.scripted_opponent = _scripted.parse_opponents(scripted_opponent)
+        if self.opponent_pool > 0 and self.scripted_opponent:
+            raise ValueError("a scripted opponent and an opponent pool on the same agent are not supported "
+                             "(opponent_pool stores both agents)")
         # set by the train_* functions from the env (CPPO_main.py:99-101)
         self.state_dim = 18
         self.action_dim = 3
@@ -394,6 +408,9 @@ class VecTrainer:
         self.last_assignment = None
         if int(getattr(args, "opponent_pool", 0)) > 0:
             self._setup_pools(args)
+        self._laws = {}                                      # agent -> ScriptedLaw (satrl/scripted.py)
+        for agent, law in dict(getattr(args, "scripted_opponent", None) or {}).items():
+            self.set_scripted_opponent(agent, law)
         rs = getattr(args, "reset_seed", None)
         self.reset_seed = self.seed if rs is None else int(rs)
         self.set_reset_spread(getattr(args, "reset_spread", None))
@@ -497,6 +514,36 @@ class VecTrainer:
             if d.get(k) is None:
                 raise ValueError(f"no {k} pool in this state")
             p.load_state(d[k])
+
+    # -- scripted opponents (satrl/scripted.py) ------------------------------------------------
+    @property
+    def scripted_opponents(self):
+        """{agent: ScriptedLaw} of the agents that act with a law while frozen."""
+        return dict(self._laws)
+
+    def set_scripted_opponent(self, agent, law):
+        """Attach `law` (a ScriptedLaw, a builder's name, or None to detach) to
+        `agent` ("pursuer" | "evader"): the agent acts with it whenever it is
+        the frozen one.  Attaching, detaching or replacing the law object drops
+        the captured rollout graphs (they hold the launch and the block's
+        address); changing an attached law's values (ScriptedLaw.update) never
+        does.  The curriculum hook: train against a law, detach it, go on with
+        self-play."""
+        if agent not in _scripted.AGENTS:
+            raise ValueError(f"agent is one of {_scripted.AGENTS}, got {agent!r}")
+        if law is not None:
+            law = _scripted.as_law(law)
+            if self.pools is not None:
+                raise ValueError("a scripted opponent and an opponent pool on the same agent are not supported "
+                                 "(opponent_pool stores both agents)")
+            law.block(self.device)
+        if self._laws.get(agent) is law:
+            return
+        if law is None:
+            del self._laws[agent]
+        else:
+            self._laws[agent] = law
+        self._graphs.clear()
 
     def set_reset_spread(self, spread, seed=None):
         """The box the env's resets draw their starts from (args_param
@@ -659,7 +706,12 @@ class VecTrainer:
         else:                                    # evader transitions are stored (CPPO_main.py:210)
             pa, plp, ea, elp = self.other_a, self.other_lp, buf.act[t], buf.logp[t]
         # both agents act on s (CPPO_main.py:122-123): one fused launch, pursuer = agent 0
-        if self.pools is None:
+        law = self._laws.get(self.frozen_agent)
+        if law is not None:                      # the frozen agent's law on the raw row, the learner's MLP alone
+            policy_act_scripted(self.learner.H, obs_t, self.obs_raw if self.obs_norm else obs_t, self.learner.P,
+                                self.flag, 1.6, self.seed, self.env_offset, t, buf.act[t], buf.logp[t], law,
+                                self.other_a, step_base=self.step_base)
+        elif self.pools is None:
             policy_act(self.pursuer.H, obs_t, self.pursuer.P, self.evader.P, 1.6, self.seed, self.env_offset, t,
                        pa, plp, ea, elp, step_base=self.step_base)
         else:                                    # the frozen agent acts, per 32-env block, with its member of the pool
@@ -751,7 +803,10 @@ class VecTrainer:
                 ep = self.env.episode_index()
                 st = self.env.stats.clone()
                 ret = self.env.episode_return() if self._loaded else None
+                raw = self.obs_raw.clone() if self.obs_norm else None    # step 0's raw row: a scripted law reads it
                 self._policy_step(0)
+                if raw is not None:
+                    self.obs_raw.copy_(raw)
                 self.env.set_state(f, i)
                 self.env.set_episode_index(ep)
                 self.env.stats.copy_(st)
@@ -891,6 +946,8 @@ class VecTrainer:
                 s = p.state()
                 s["storage"] = s["storage"].numpy()
                 d["pools"][k] = s
+        if self._laws:                           # (optional: a run without laws writes what it always wrote)
+            d["scripted"] = {k: law.state() for k, law in self._laws.items()}
         return d
 
     def load_state_dict(self, d):
@@ -941,6 +998,16 @@ class VecTrainer:
                                                                       ("K", "H", "cursor", "added", "seed"))
                 s["storage"] = torch.from_numpy(np.ascontiguousarray(s["storage"]))
                 p.load_state(s)
+        saved_laws = d.get("scripted") or {}
+        for k in _scripted.AGENTS:               # a state without the entry: no laws
+            if k not in saved_laws:
+                self.set_scripted_opponent(k, None)
+            elif k in self._laws:                # in place: the captured graphs stay
+                st = saved_laws[k]
+                self._laws[k].update(G=np.asarray(st["G"]), b=np.asarray(st["b"]),
+                                     max_action=float(np.asarray(st["max_action"]).item()))
+            else:
+                self.set_scripted_opponent(k, _scripted.ScriptedLaw.from_state(saved_laws[k]))
         if "gen" in d:
             self.gen.set_state(torch.from_numpy(np.ascontiguousarray(d["gen"], dtype=np.uint8)))
         else:
@@ -1032,11 +1099,23 @@ class VecTrainer:
         the per-step streams (EvalResult.streams).  opponent=k: the frozen
         agent (the one this Flag does not train) acts with slot k of its
         opponent pool instead of its live parameters (IndexError for a slot
-        that is not filled, ValueError without a pool).  No state of the
+        that is not filled, ValueError without a pool).  opponent="scripted":
+        the frozen agent acts with its scripted law (ValueError if it has
+        none); opponent=<ScriptedLaw>: with that law, on the evaluator's raw
+        observation (satrl/scripted.py).  No state of the
         trainer changes.  Under data parallelism each rank evaluates its own
         envs; results are not reduced across ranks."""
         from .evaluate import VecEvaluator
-        if opponent is not None:
+        if isinstance(opponent, str):
+            if opponent != "scripted":
+                raise ValueError(f"opponent is a pool slot, 'scripted' or a ScriptedLaw, got {opponent!r}")
+            opponent = self._laws.get(self.frozen_agent)
+            if opponent is None:
+                raise ValueError(f"evaluate(opponent='scripted'): the frozen agent ({self.frozen_agent}) has no "
+                                 "scripted law")
+        if isinstance(opponent, _scripted.ScriptedLaw):
+            opponent.block(self.device)
+        elif opponent is not None:
             if self.pools is None:
                 raise ValueError("evaluate(opponent=k) needs an opponent pool (args.opponent_pool > 0)")
             self.pools[self.frozen_agent].slot(opponent)         # IndexError for a slot that is not filled
