@@ -424,6 +424,9 @@ int satrl_span_probe(void* buf, int64_t bytes, void* stream);
 int64_t satrl_span_probe_launches(void);
 int satrl_span_probe_launch(int64_t i, int* kind, int64_t* word_offset, int64_t* waves);
 
+/* Every negative return of a satrl_* entry point (this header, satrl_peer.h,
+ * satrl_rollout.h) leaves "<entry point>: <reason>" in one per-thread slot;
+ * satrl_ppo_last_error and satrl_last_error both return it.               */
 const char* satrl_ppo_last_error(void);
 
 #ifdef __cplusplus

@@ -102,6 +102,8 @@ int satrl_episode_record(int64_t N, const double* reward, const uint8_t* done, c
                          const float* ea, double capture_reward, double* rec_f64, int32_t* rec_i32, int32_t* alive,
                          void* stream);
 
+/* "<entry point>: <reason>" of this thread's last refused satrl_* call (the
+ * slot satrl_ppo_last_error of satrl_ppo.h returns too).                  */
 const char* satrl_last_error(void);
 
 #ifdef __cplusplus

@@ -25,14 +25,13 @@
 #include <vector>
 
 #include "philox_device.h"
+#include "satrl_error.h"
 #include "span_probe.h"
 #include "satrl_ppo.h"
 #include "satrl_peer.h"
 #include "scripted_device.h"
 
 namespace {
-
-thread_local std::string g_err;
 
 #ifdef SATRL_PHASE_PROBE
 // development-only phase stamps (tools/_probe/phase_probe.py), never in the
@@ -2943,89 +2942,129 @@ int n_adam_blocks(int H, int net) {
 
 bool valid_h(int H) { return H == 64 || H == 128 || H == 256; }
 
+// What every entry point below takes its refusals, width dispatch and launch
+// check from.  A refusal is satrl_error.h's fail(code, entry point, reason); the
+// entry point passes __func__, also to a checker or launcher it shares with others.
+using satrl_err::fail;
+using satrl_err::grid_of;
+using satrl_err::launch;
+using satrl_err::launched;
+using satrl_err::null_arg;
+using std::to_string;
+
+// A width as its compile-time pair: f(Width<H, waves per workgroup>{}) of a
+// validated H.  The H 256 wave count belongs to the kernel family, so the call
+// site states it (kPolNW: policy / diagnostics, kNW256: rowpass).
+template <int H_, int NW_>
+struct Width { static constexpr int H = H_, NW = NW_; };
+template <int NW256, class F>
+auto with_width(int H, F&& f) {
+  if (H == 64) return f(Width<64, 4>{});
+  if (H == 128) return f(Width<128, 8>{});
+  return f(Width<256, NW256>{});
+}
+template <int NW256>
+int waves_of(int H) { return with_width<NW256>(H, [](auto w) { return decltype(w)::NW; }); }
+
+// a scalar argument outside lo .. hi, refused under its name
+int outside(const char* who, const char* name, int64_t v, int64_t lo, int64_t hi) {
+  if (v >= lo && v <= hi) return 0;
+  return fail(-1, who, name + (" " + to_string(v)) + " is outside " + to_string(lo) + " .. " + to_string(hi));
+}
+// The refusals the width-taking entry points share, in this order; 0 when none
+// applies.  `widths` is the set the entry point takes, as the OR of them; `n`
+// its row count under its own name (1 where it has none); `net` 0 where it has none.
+constexpr int kAnyH = 64 | 128 | 256, kFusedH = 64 | 128;
+int refuse(const char* who, int H, int widths, int64_t n, const char* n_name, int net,
+           const satrl_err::Ptrs& need = {"", {}}) {
+  if (!valid_h(H) || !(H & widths))
+    return fail(-1, who, "H " + to_string(H) + " is not " +
+                             (widths == kAnyH ? "64/128/256" : widths == kFusedH ? "64/128" : "256"));
+  if (n <= 0) return fail(-1, who, std::string(n_name) + " " + to_string(n) + " is empty (<= 0)");
+  if (int rc = outside(who, "net", net, -1, 1)) return rc;
+  return null_arg(who, need);
+}
+
 // Caller-buffer capacity checks of the C-ABI (before any launch).  A one-net
 // call (net 1) addresses the second half of a [2][...] buffer, so only net 0
 // may pass half the size.
 int64_t nets_span(int net) { return net == 0 ? 1 : 2; }
 // p2 [2][S][H][H] f32 split-K slabs
-bool p2_fits(int H, int net, int S, int64_t p2_floats, const char* who) {
+int p2_fits(const char* who, int H, int net, int S, int64_t p2_floats) {
   const int64_t need = nets_span(net) * (int64_t)S * H * H;
-  if (p2_floats >= need) return true;
-  g_err = std::string(who) + ": p2 holds " + std::to_string(p2_floats) + " floats, " + std::to_string(S) +
-          " splits need " + std::to_string(need);
-  return false;
+  if (p2_floats >= need) return 0;
+  return fail(-1, who, "p2 holds " + to_string(p2_floats) + " floats, " + to_string(S) + " splits need " +
+                           to_string(need));
 }
 // the k-packed planes u16 [2][3][kx_rows(mb)][H] (satrl_ppo_kx_elems)
-bool kx_fits(int H, int mb, int net, int64_t kx_elems, const char* who) {
+int kx_fits(const char* who, int H, int mb, int net, int64_t kx_elems) {
   const int64_t need = nets_span(net) * 3 * kx_rows(mb) * H;
-  if (kx_elems >= need) return true;
-  g_err = std::string(who) + ": the H1x / dZ2x planes hold " + std::to_string(kx_elems) + " elements, mb " +
-          std::to_string(mb) + " needs " + std::to_string(need);
-  return false;
+  if (kx_elems >= need) return 0;
+  return fail(-1, who, "the H1x / dZ2x planes hold " + to_string(kx_elems) + " elements, mb " +
+                           to_string(mb) + " needs " + to_string(need));
 }
-
-#define LAUNCH_CHECK()                                                      \
-  do {                                                                      \
-    hipError_t e_ = hipGetLastError();                                      \
-    if (e_ != hipSuccess) { g_err = hipGetErrorString(e_); return -2; }     \
-  } while (0)
+// *per: the rows one of S splits of `rows` takes, a multiple of `round`; no split may be empty
+int split_size(const char* who, int S, int rows, int round, const char* query, int* per) {
+  if (S < 1) return fail(-1, who, "S " + to_string(S) + " < 1");
+  *per = ((rows + S - 1) / S + round - 1) / round * round;
+  if ((int64_t)*per * (S - 1) < rows) return 0;
+  return fail(-1, who, to_string(S) + " splits leave an empty split: use " + query);
+}
+// Workgroups of kernel k at `threads` threads that can be resident at once on
+// the current device, CUs x workgroups per CU; false when a query fails.
+struct Residency {
+  int cus = 0, per_cu = 0;
+  int blocks() const { return cus * per_cu; }
+};
+template <class K>
+bool residency(K k, int threads, Residency* r) {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess &&
+         hipDeviceGetAttribute(&r->cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+         hipOccupancyMaxActiveBlocksPerMultiprocessor(&r->per_cu, k, threads, 0) == hipSuccess;
+}
 
 using satrl_span::launch_span;
-// policy_kernel<H, NW, MODE> at width H on grid g, probed as span kind `kind`
+// policy_kernel<H, NW, MODE> over N rows of `nag` agents, probed as span kind `kind`
 template <int MODE, class... A>
-void launch_policy(int H, int kind, dim3 g, void* stream, A... args) {
-  const int nw = H == 64 ? 4 : H == 128 ? 8 : kPolNW;
-  unsigned long long* sp = satrl_span::take(kind, (int64_t)g.x * nw);
-  if (H == 64)
-    launch_span(policy_kernel<64, 4, MODE, true>, policy_kernel<64, 4, MODE>, sp, g, dim3(nw * 64), stream, args...);
-  else if (H == 128)
-    launch_span(policy_kernel<128, 8, MODE, true>, policy_kernel<128, 8, MODE>, sp, g, dim3(nw * 64), stream, args...);
-  else
-    launch_span(policy_kernel<256, kPolNW, MODE, true>, policy_kernel<256, kPolNW, MODE>, sp, g, dim3(nw * 64), stream,
-                args...);
+int launch_policy(const char* who, int H, int kind, int nag, int64_t N, void* stream, A... args) {
+  dim3 g;
+  if (int rc = grid_of(who, nag * ((N + kPolRows - 1) / kPolRows), &g)) return rc;
+  with_width<kPolNW>(H, [&](auto w) {
+    using W = decltype(w);
+    launch_span(policy_kernel<W::H, W::NW, MODE, true>, policy_kernel<W::H, W::NW, MODE>,
+                satrl_span::take(kind, (int64_t)g.x * W::NW), g, dim3(W::NW * 64), stream, N, args...);
+  });
+  return launched(who);
 }
+// the two Philox keys of both agents' action streams
+struct PolicyKeys {
+  uint32_t k00, k01, k10, k11;
+  explicit PolicyKeys(uint64_t seed) {
+    philox_key(seed, 0, k00, k01);
+    philox_key(seed, 1, k10, k11);
+  }
+};
 // the launch of both fused forms (MODE 0: act + logp, MODE 2: actions only)
 template <int MODE>
 int launch_policy_scripted(const char* who, int H, int64_t N, const float* obs, const float* obs_law,
-                                  const float* P, int agent, float max_action, int det, uint64_t seed,
-                                  int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act,
-                                  float* logp, const satrl_scripted_law* law, float* act_scripted, void* stream) {
-  const char* why = nullptr;
-  if (!valid_h(H) || N <= 0 || !obs || !P || !act || (MODE == 0 && !logp))
-    why = MODE == 0 ? "H not 64/128/256, N <= 0, or a NULL obs, P, act or logp"
-                    : "H not 64/128/256, N <= 0, or a NULL obs, P or act";
-  else if (!obs_law || !law || !act_scripted)
-    why = "a NULL obs_law, law or act_scripted";
-  else if (agent != 0 && agent != 1)
-    why = "agent is 0 or 1";
-  else if (det != 0 && det != 1)
-    why = "det is 0 or 1";
-  if (why) {
-    g_err = std::string(who) + ": " + why;
-    return -1;
-  }
+                           const float* P, int agent, float max_action, int det, uint64_t seed, int64_t env_offset,
+                           uint64_t step, const uint64_t* step_base, float* act, float* logp,
+                           const satrl_scripted_law* law, float* act_scripted, void* stream) {
+  if (int rc = refuse(who, H, kAnyH, N, "N", 0, SATRL_PTRS(obs, P, act))) return rc;
+  if (MODE == 0 && !logp) return fail(-1, who, "logp is NULL");
+  if (!obs_law || !law || !act_scripted) return fail(-1, who, "a NULL obs_law, law or act_scripted");
+  if (agent != 0 && agent != 1) return fail(-1, who, "agent is 0 or 1");
+  if (det != 0 && det != 1) return fail(-1, who, "det is 0 or 1");
   uint32_t k0, k1;
   philox_key(seed, (uint32_t)agent, k0, k1);                       // the learner's own key stream
-  const int nw = H == 64 ? 4 : H == 128 ? 8 : kPolNW;
   const int64_t nblk = (N + kPolRows - 1) / kPolRows;
-  const int64_t ntail = (N + nw * 64 - 1) / (nw * 64);
-  if (nblk + ntail > 0x7FFFFFFF) {
-    g_err = std::string(who) + ": N is too large for one grid";
-    return -1;
-  }
-  const dim3 g((unsigned)(nblk + ntail));
-  hipStream_t s = (hipStream_t)stream;
-  if (H == 64)
-    hipLaunchKernelGGL((policy_scripted_kernel<64, 4, MODE>), g, dim3(256), 0, s, N, obs, P, obs_law, law,
-                       act_scripted, (int)nblk, max_action, k0, k1, env_offset, step, step_base, act, logp, det);
-  else if (H == 128)
-    hipLaunchKernelGGL((policy_scripted_kernel<128, 8, MODE>), g, dim3(512), 0, s, N, obs, P, obs_law, law,
-                       act_scripted, (int)nblk, max_action, k0, k1, env_offset, step, step_base, act, logp, det);
-  else
-    hipLaunchKernelGGL((policy_scripted_kernel<256, kPolNW, MODE>), g, dim3(kPolNW * 64), 0, s, N, obs, P, obs_law,
-                       law, act_scripted, (int)nblk, max_action, k0, k1, env_offset, step, step_base, act, logp, det);
-  LAUNCH_CHECK();
-  return 0;
+  return with_width<kPolNW>(H, [&](auto w) {
+    constexpr int NT = decltype(w)::NW * 64;                       // the law's rows: one per thread of the tail blocks
+    return launch(who, policy_scripted_kernel<decltype(w)::H, decltype(w)::NW, MODE>, nblk + (N + NT - 1) / NT, NT,
+                  stream, N, obs, P, obs_law, law, act_scripted, (int)nblk, max_action, k0, k1, env_offset, step,
+                  step_base, act, logp, det);
+  });
 }
 
 // the two instantiations of a rowpass_kernel, {probed, plain}
@@ -3231,7 +3270,7 @@ unsigned long long* satrl_span::take(int kind, int64_t waves) {
 extern "C" {
 
 int satrl_ppo_layout(int H, int64_t* off) {
-  if (!valid_h(H) || !off) return -1;
+  if (int rc = refuse(__func__, H, kAnyH, 1, "", 0, SATRL_PTRS(off))) return rc;
   const Layout L = layout(H);
   off[SATRL_PPO_OFF_W2] = L.W2;
   off[SATRL_PPO_OFF_W1] = L.W1;
@@ -3314,16 +3353,20 @@ static void plan_fill(int H, int mb, int net, satrl_ppo_plan* p) {
   p->rows_floats = 2LL * mb * H;
 }
 
-int satrl_ppo_step_plan(int H, int mb, int net, satrl_ppo_plan* plan) {
-  if (!valid_h(H) || mb <= 0 || net < -1 || net > 1 || !plan) return -1;
+// the checked plan: satrl_ppo_step_plan, and every size query that reads one field of it
+static int plan_of(const char* who, int H, int widths, int mb, int net, satrl_ppo_plan* plan) {
+  if (int rc = refuse(who, H, widths, mb, "mb", net, SATRL_PTRS(plan))) return rc;
   plan_fill(H, mb, net, plan);
   return 0;
 }
 
+int satrl_ppo_step_plan(int H, int mb, int net, satrl_ppo_plan* plan) {
+  return plan_of(__func__, H, kAnyH, mb, net, plan);
+}
+
 int satrl_ppo_sizes(int H, int mb, int64_t* nwg, int64_t* nblk) {
-  if (!valid_h(H) || mb <= 0) return -1;
   satrl_ppo_plan p;
-  plan_fill(H, mb, -1, &p);
+  if (int rc = plan_of(__func__, H, kAnyH, mb, -1, &p)) return rc;
   if (nwg) *nwg = p.slab_blocks;
   if (nblk) *nblk = p.norm_blocks;
   return 0;
@@ -3335,33 +3378,38 @@ int satrl_ppo_sizes(int H, int mb, int64_t* nwg, int64_t* nblk) {
 static bool cs_fits(int mb) {
   if (mb > kCsMaxMb) return false;
   static const int resident = [] {
-    int dev = 0, per_cu = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rowpass_cs_kernel<false>, kCsWaves * 64, 0) !=
-            hipSuccess)
-      return 0;
-    return per_cu * cus;
+    Residency r;
+    return residency(rowpass_cs_kernel<false>, kCsWaves * 64, &r) ? r.blocks() : 0;
   }();
   return (2 * ((mb + kRowsShort - 1) / kRowsShort) + 7) / 8 * 32 <= resident;
 }
 
-// every rowpass launch: `out` says what it writes for dW2 (kRpOutDw2, H <= 128:
+// every rowpass entry point: `out` says what it writes for dW2 (kRpOutDw2, H <= 128:
 // the block's dW2 partial to p2 instead of H1 / dZ2; kRpOutPlanes, H = 256: H1 /
-// dZ2 are the k-packed planes); ratio (nullable) receives the actor's per-row ratio
-static int launch_rowpass(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
-                          const void* W2X, float epsilon, float ent_coef, float max_action, float* H1, float* dZ2,
-                          float* ptail, float* pw1, float* p2, float* ratio, RpOut out, RpBlock block, void* stream) {
+// dZ2 are the k-packed planes) and with it which widths and outputs the call needs;
+// `cap` is the caller's capacity of p2 or of the planes; ratio (nullable) receives
+// the actor's per-row ratio
+static int launch_rowpass(const char* who, int H, int mb, int net, const float* src, const int64_t* idx,
+                          const float* P, const void* W2X, float epsilon, float ent_coef, float max_action, float* H1,
+                          float* dZ2, float* ptail, float* pw1, float* p2, int64_t cap, float* ratio, RpOut out,
+                          RpBlock block, void* stream) {
+  const bool fdw2 = out == kRpOutDw2, kx = out == kRpOutPlanes;
+  if (int rc = refuse(who, H, fdw2 ? kFusedH : kx ? 256 : kAnyH, mb, "mb", net, SATRL_PTRS(src, P, W2X, ptail, pw1)))
+    return rc;
+  // what it hands to dW2, and the caller's capacity for it (p2: one slab per row block)
+  if (int rc = fdw2 ? null_arg(who, SATRL_PTRS(p2)) : null_arg(who, {kx ? "H1x, dZ2x" : "H1, dZ2", {H1, dZ2}}))
+    return rc;
+  if (int rc = fdw2 ? p2_fits(who, H, net, n_head_wg(H, mb), cap) : kx ? kx_fits(who, H, mb, net, cap) : 0) return rc;
   // the plan's kernel; the column split only when its grid is resident (else
   // the 16-wave kernel on the same 16-row blocks: the same bits)
   int kind = rowpass_kind(H, mb, net, out, block);
   if (kind == SATRL_PPO_RP_CS && !cs_fits(mb)) kind = SATRL_PPO_RP_WG16;
-  const bool cs = kind == SATRL_PPO_RP_CS, fdw2 = out == kRpOutDw2, kx = out == kRpOutPlanes;
+  const bool cs = kind == SATRL_PPO_RP_CS;
   const int R = rp_rows(kind), nrb = (mb + R - 1) / R;
   dim3 g((net < 0 ? 2 : 1) * nrb);   // (row block, net) pairs, or row blocks of one net
-  // waves per workgroup: one 16-column tile per wave for both 16-row tiles
   const float inv_mb = 1.0f / (float)mb;
-  const int nw = H == 64 ? 4 : H == 128 ? 8 : 16;                  // waves per workgroup
+  // waves per workgroup: one 16-column tile per wave for both 16-row tiles
+  const int nw = waves_of<kNW256>(H);
   // (the column-split kernel: groups of kCsSplit workgroups dealt in windows of 32 blocks)
   const dim3 gc((unsigned)((2 * nrb + 7) / 8 * 32));
   unsigned long long* sp =
@@ -3370,92 +3418,80 @@ static int launch_rowpass(int H, int mb, int net, const float* src, const int64_
     launch_span(k.first, k.second, sp, g, dim3(nw * 64), stream, mb, net, src, idx, P, W2X, H1, dZ2, epsilon,
                 ent_coef, max_action, ptail, pw1, p2, nrb, ratio, inv_mb);
   };
-  if (H == 64)
-    fdw2 ? rp(rowpass_k<64, 4, kRows, true, false>()) : rp(rowpass_k<64, 4, kRows, false, false>());
-  else if (H == 128)
-    fdw2 ? rp(rowpass_k<128, 8, kRows, true, false>()) : rp(rowpass_k<128, 8, kRows, false, false>());
-  else if (cs)
-    launch_span(rowpass_cs_kernel<true>, rowpass_cs_kernel<false>, sp, gc, dim3(kCsWaves * 64), stream, mb, src, idx, P,
-                static_cast<const float*>(W2X), epsilon, ent_coef, max_action, reinterpret_cast<unsigned short*>(H1),
-                reinterpret_cast<unsigned short*>(dZ2), ptail, pw1, inv_mb);
-  else if (kind == SATRL_PPO_RP_WG16)
-    kx ? rp(rowpass_k<256, 16, kRowsShort, false, true>()) : rp(rowpass_k<256, 16, kRowsShort, false, false>());
-  else if (kind == SATRL_PPO_RP_WG32_HANDOFF)
-    rp(rowpass_k<256, kNW256, kRows, false, true, true>());
-  else
-    kx ? rp(rowpass_k<256, kNW256, kRows, false, true>()) : rp(rowpass_k<256, kNW256, kRows, false, false>());
-  LAUNCH_CHECK();
-  return 0;
+  with_width<kNW256>(H, [&](auto w) {
+    using W = decltype(w);
+    if constexpr (W::H != 256)
+      fdw2 ? rp(rowpass_k<W::H, W::NW, kRows, true, false>()) : rp(rowpass_k<W::H, W::NW, kRows, false, false>());
+    else if (cs)
+      launch_span(rowpass_cs_kernel<true>, rowpass_cs_kernel<false>, sp, gc, dim3(kCsWaves * 64), stream, mb, src, idx,
+                  P, static_cast<const float*>(W2X), epsilon, ent_coef, max_action,
+                  reinterpret_cast<unsigned short*>(H1), reinterpret_cast<unsigned short*>(dZ2), ptail, pw1, inv_mb);
+    else if (kind == SATRL_PPO_RP_WG16)
+      kx ? rp(rowpass_k<256, W::NW, kRowsShort, false, true>()) : rp(rowpass_k<256, W::NW, kRowsShort, false, false>());
+    else if (kind == SATRL_PPO_RP_WG32_HANDOFF)
+      rp(rowpass_k<256, W::NW, kRows, false, true, true>());
+    else
+      kx ? rp(rowpass_k<256, W::NW, kRows, false, true>()) : rp(rowpass_k<256, W::NW, kRows, false, false>());
+  });
+  return launched(who);
 }
 
 int satrl_ppo_rowpass(int H, int mb, int net, const float* src, const int64_t* idx, const float* P, const void* W2X,
                       float epsilon, float ent_coef, float max_action, float* H1, float* dZ2, float* ptail,
                       float* pw1, void* stream) {
-  if (!valid_h(H) || mb <= 0 || net < -1 || net > 1 || !src || !P || !W2X || !H1 || !dZ2 || !ptail || !pw1)
-    return -1;
-  return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, H1, dZ2, ptail, pw1, nullptr,
-                        nullptr, kRpOutRows, kRpBlockByMb, stream);
+  return launch_rowpass(__func__, H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, H1, dZ2,
+                        ptail, pw1, nullptr, 0, nullptr, kRpOutRows, kRpBlockByMb, stream);
 }
 
 int satrl_ppo_rowpass_ratio(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
                             const void* W2X, float epsilon, float ent_coef, float max_action, float* H1, float* dZ2,
                             float* ptail, float* pw1, float* ratio, void* stream) {
-  if (!valid_h(H) || mb <= 0 || net < -1 || net > 1 || !src || !P || !W2X || !H1 || !dZ2 || !ptail || !pw1 ||
-      !ratio)
-    return -1;
-  return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, H1, dZ2, ptail, pw1, nullptr,
-                        ratio, kRpOutRows, kRpBlockByMb, stream);
+  if (!ratio) return fail(-1, __func__, "ratio is NULL");
+  return launch_rowpass(__func__, H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, H1,
+                        dZ2, ptail, pw1, nullptr, 0, ratio, kRpOutRows, kRpBlockByMb, stream);
 }
 
 int satrl_ppo_row_blocks(int H, int mb) {
   satrl_ppo_plan p;
-  return satrl_ppo_step_plan(H, mb, -1, &p) == 0 ? p.row_blocks : -1;
+  return plan_of(__func__, H, kAnyH, mb, -1, &p) ? -1 : p.row_blocks;
 }
 
 int satrl_ppo_rowpass_dw2(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
                           const void* W2X, float epsilon, float ent_coef, float max_action, float* p2,
                           int64_t p2_floats, float* ptail, float* pw1, void* stream) {
-  if ((H != 64 && H != 128) || mb <= 0 || net < -1 || net > 1 || !src || !P || !W2X || !p2 || !ptail || !pw1)
-    return -1;
-  if (!p2_fits(H, net, n_head_wg(H, mb), p2_floats, "satrl_ppo_rowpass_dw2")) return -1;   // one slab per row block
-  return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, nullptr, nullptr, ptail, pw1, p2,
-                        nullptr, kRpOutDw2, kRpBlockByMb, stream);
+  return launch_rowpass(__func__, H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, nullptr,
+                        nullptr, ptail, pw1, p2, p2_floats, nullptr, kRpOutDw2, kRpBlockByMb, stream);
 }
 
 int64_t satrl_ppo_kx_elems(int H, int mb) {
   satrl_ppo_plan p;
-  return H == 256 && satrl_ppo_step_plan(H, mb, -1, &p) == 0 ? p.kx_elems : -1;
+  return plan_of(__func__, H, 256, mb, -1, &p) ? -1 : p.kx_elems;
 }
 
 int satrl_ppo_rowpass_kx(int H, int mb, int net, const float* src, const int64_t* idx, const float* P, const void* W2X,
                          float epsilon, float ent_coef, float max_action, void* H1x, void* dZ2x, int64_t kx_elems,
                          float* ptail, float* pw1, void* stream) {
-  if (H != 256 || mb <= 0 || net < -1 || net > 1 || !src || !P || !W2X || !H1x || !dZ2x ||
-      !ptail || !pw1)
-    return -1;
-  if (!kx_fits(H, mb, net, kx_elems, "satrl_ppo_rowpass_kx")) return -1;
-  return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, static_cast<float*>(H1x),
-                        static_cast<float*>(dZ2x), ptail, pw1, nullptr, nullptr, kRpOutPlanes, kRpBlockByMb, stream);
+  return launch_rowpass(__func__, H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action,
+                        static_cast<float*>(H1x), static_cast<float*>(dZ2x), ptail, pw1, nullptr, kx_elems, nullptr,
+                        kRpOutPlanes, kRpBlockByMb, stream);
 }
 
 int satrl_ppo_rowpass_kx32(int H, int mb, int net, const float* src, const int64_t* idx, const float* P,
                            const void* W2X, float epsilon, float ent_coef, float max_action, void* H1x, void* dZ2x,
                            int64_t kx_elems, float* ptail, float* pw1, float* ratio, void* stream) {
-  if (H != 256 || mb <= 0 || net < -1 || net > 1 || !src || !P || !W2X || !H1x || !dZ2x ||
-      !ptail || !pw1)
-    return -1;
-  if (!kx_fits(H, mb, net, kx_elems, "satrl_ppo_rowpass_kx32")) return -1;
-  return launch_rowpass(H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action, static_cast<float*>(H1x),
-                        static_cast<float*>(dZ2x), ptail, pw1, nullptr, ratio, kRpOutPlanes, kRpBlock32, stream);
+  return launch_rowpass(__func__, H, mb, net, src, idx, P, W2X, epsilon, ent_coef, max_action,
+                        static_cast<float*>(H1x), static_cast<float*>(dZ2x), ptail, pw1, nullptr, kx_elems, ratio,
+                        kRpOutPlanes, kRpBlock32, stream);
 }
 
 int satrl_ppo_rowpass_sync(int mode) {
-  if (mode < -1 || mode > 1) return -1;
+  if (int rc = outside(__func__, "mode", mode, -1, 1)) return rc;
   return mode < 0 ? g_rp_sync.load(std::memory_order_relaxed) : g_rp_sync.exchange(mode, std::memory_order_relaxed);
 }
 
 int satrl_ppo_rowpass_error(int* err, double timeout_s, void* stream) {
-  if (!err || !(timeout_s > 0)) return -1;
+  if (int rc = null_arg(__func__, SATRL_PTRS(err))) return rc;
+  if (!(timeout_s > 0)) return fail(-1, __func__, "timeout_s is not positive: no deadline");
   hipStream_t s = (hipStream_t)stream;
   // the error word lands in pinned memory behind an event that is polled
   // against the host deadline: a stream that never drains (e.g. a collective
@@ -3472,111 +3508,97 @@ int satrl_ppo_rowpass_error(int* err, double timeout_s, void* stream) {
       hipGetSymbolAddress(&pe, HIP_SYMBOL(g_cs_err)) != hipSuccess ||
       hipGetSymbolAddress(&pc, HIP_SYMBOL(g_cs_ctr)) != hipSuccess ||
       hipMemcpyAsync(host, pe, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipEventRecord(ev, s) != hipSuccess) {
-    g_err = "satrl_ppo_rowpass_error: reading the exchange error word failed";
-    return -1;
-  }
+      hipEventRecord(ev, s) != hipSuccess)
+    return fail(-1, __func__, "reading the exchange error word failed");
   const auto t0 = std::chrono::steady_clock::now();
   for (;;) {
     const hipError_t q = hipEventQuery(ev);
     if (q == hipSuccess) break;
-    if (q != hipErrorNotReady) {
-      g_err = "satrl_ppo_rowpass_error: waiting for the stream failed";
-      return -1;
-    }
+    if (q != hipErrorNotReady) return fail(-1, __func__, "waiting for the stream failed");
     if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s) {
       host = nullptr;
       ev = nullptr;
-      g_err = "satrl_ppo_rowpass_error: the stream did not drain within the deadline";
-      return -2;
+      return fail(-2, __func__, "the stream did not drain within the deadline");
     }
     std::this_thread::sleep_for(std::chrono::microseconds(20));
   }
   const unsigned e = host[0];
   *err = e != 0;
   if (e != 0 && (hipMemsetAsync(pe, 0, sizeof(g_cs_err), s) != hipSuccess ||
-                 hipMemsetAsync(pc, 0, sizeof(g_cs_ctr), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) {
-    g_err = "satrl_ppo_rowpass_error: re-arming the exchange state failed";
-    return -1;
-  }
+                 hipMemsetAsync(pc, 0, sizeof(g_cs_ctr), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess))
+    return fail(-1, __func__, "re-arming the exchange state failed");
   return 0;
 }
 
 int satrl_ppo_rowpass_fault_inject(int group, unsigned value, void* stream) {
-  if (group < 0 || group >= kCsMaxGroups) return -1;
+  if (int rc = outside(__func__, "group", group, 0, kCsMaxGroups - 1)) return rc;
   hipStream_t s = (hipStream_t)stream;
   void* pc = nullptr;
   if (hipGetSymbolAddress(&pc, HIP_SYMBOL(g_cs_ctr)) != hipSuccess ||
       hipMemcpyAsync(static_cast<unsigned*>(pc) + (size_t)group * 32, &value, sizeof(value), hipMemcpyHostToDevice, s) !=
           hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    g_err = "satrl_ppo_rowpass_fault_inject: writing the exchange counter failed";
-    return -1;
-  }
+      hipStreamSynchronize(s) != hipSuccess)
+    return fail(-1, __func__, "writing the exchange counter failed");
   return 0;
 }
 
 int satrl_ppo_dw2_kx_splits(int H, int mb, int net) {
   satrl_ppo_plan p;
-  return H == 256 && satrl_ppo_step_plan(H, mb, net, &p) == 0 ? p.splits : -1;
+  return plan_of(__func__, H, 256, mb, net, &p) ? -1 : p.splits;
+}
+
+// what both k-packed dW2 entry points refuse; *kr: the rows of one split
+static int dw2_kx_check(const char* who, int H, int mb, int net, int S, const void* H1x, const void* dZ2x,
+                        int64_t kx_elems, float* p2, int64_t p2_floats, int* kr) {
+  if (int rc = refuse(who, H, 256, mb, "mb", net, SATRL_PTRS(H1x, dZ2x, p2))) return rc;
+  if (int rc = split_size(who, S, (int)kx_rows(mb), 32, "satrl_ppo_dw2_kx_splits", kr)) return rc;   // whole chunks
+  if (int rc = kx_fits(who, H, mb, net, kx_elems)) return rc;
+  return p2_fits(who, H, net, S, p2_floats);
 }
 
 int satrl_ppo_dw2_kx(int H, int mb, int net, int S, const void* H1x, const void* dZ2x, int64_t kx_elems, float* p2,
                      int64_t p2_floats, void* stream) {
-  if (H != 256 || mb <= 0 || net < -1 || net > 1 || S < 1 || !H1x || !dZ2x || !p2) return -1;
-  const int nch = (int)(kx_rows(mb) / 32), cps = (nch + S - 1) / S;
-  if ((int64_t)cps * (S - 1) >= nch) return -1;                  // an empty split: use satrl_ppo_dw2_kx_splits
-  if (!kx_fits(H, mb, net, kx_elems, "satrl_ppo_dw2_kx") || !p2_fits(H, net, S, p2_floats, "satrl_ppo_dw2_kx"))
-    return -1;
+  int kr = 0;
+  if (int rc = dw2_kx_check(__func__, H, mb, net, S, H1x, dZ2x, kx_elems, p2, p2_floats, &kr)) return rc;
   const dim3 g((unsigned)(kx_tiles(net) * S));
   unsigned long long* sp = satrl_span::take(satrl_span::kDw2, (int64_t)g.x * 4);
-  launch_span(dw2_kx_kernel<kKxTW, true>, dw2_kx_kernel<kKxTW>, sp, g, dim3(256), stream, mb, S, cps * 32, net,
+  launch_span(dw2_kx_kernel<kKxTW, true>, dw2_kx_kernel<kKxTW>, sp, g, dim3(256), stream, mb, S, kr, net,
               static_cast<const unsigned short*>(H1x), static_cast<const unsigned short*>(dZ2x), p2);
-  LAUNCH_CHECK();
-  return 0;
+  return launched(__func__);
 }
 
 int satrl_ppo_dw2_kx_w1(int H, int mb, int net, int S, const void* H1x, const void* dZ2x, int64_t kx_elems, float* p2,
                         int64_t p2_floats, int mode, const float* p1, const float* pt, float* G, double* nsq,
                         void* stream) {
-  if (H != 256 || mb <= 0 || net < -1 || net > 1 || S < 1 || !H1x || !dZ2x || !p2) return -1;
-  if (!(mode == 1 || mode == 3) || !p1 || !pt || !G || ((mode & 2) && !nsq)) return -1;
-  const int nch = (int)(kx_rows(mb) / 32), cps = (nch + S - 1) / S;
-  if ((int64_t)cps * (S - 1) >= nch) return -1;                  // an empty split: use satrl_ppo_dw2_kx_splits
-  if (!kx_fits(H, mb, net, kx_elems, "satrl_ppo_dw2_kx_w1") || !p2_fits(H, net, S, p2_floats, "satrl_ppo_dw2_kx_w1"))
-    return -1;
+  int kr = 0;
+  if (int rc = dw2_kx_check(__func__, H, mb, net, S, H1x, dZ2x, kx_elems, p2, p2_floats, &kr)) return rc;
+  if (mode != 1 && mode != 3) return fail(-1, __func__, "mode " + to_string(mode) + " is not 1 or 3");
+  if (int rc = null_arg(__func__, SATRL_PTRS(p1, pt, G))) return rc;
+  if ((mode & 2) && !nsq) return fail(-1, __func__, "nsq is NULL with mode 3");
   const RedGeom rg = geom(H, mb, S, net);
   const int ndw = kx_tiles(net) * S;
   const dim3 g((unsigned)(ndw + rg.nb1 + rg.nbt));
   unsigned long long* sp = satrl_span::take(satrl_span::kDw2, (int64_t)g.x * 4);
   const unsigned short *h1 = static_cast<const unsigned short*>(H1x), *dz = static_cast<const unsigned short*>(dZ2x);
-  launch_span(dw2_kx_w1_kernel<kKxTW, true>, dw2_kx_w1_kernel<kKxTW>, sp, g, dim3(256), stream, mb, S, cps * 32, net,
-              h1, dz, p2, ndw, rg, mode, p1, pt, G, nsq);
-  LAUNCH_CHECK();
-  return 0;
+  launch_span(dw2_kx_w1_kernel<kKxTW, true>, dw2_kx_w1_kernel<kKxTW>, sp, g, dim3(256), stream, mb, S, kr, net, h1, dz,
+              p2, ndw, rg, mode, p1, pt, G, nsq);
+  return launched(__func__);
 }
 
 int satrl_ppo_dw2_splits(int H, int mb) {
-  if (!valid_h(H) || mb <= 0) return -1;
-  return dw2_splits(H, mb, -1);
+  return refuse(__func__, H, kAnyH, mb, "mb", -1) ? -1 : dw2_splits(H, mb, -1);
 }
 
 int satrl_ppo_dw2(int H, int mb, int net, int S, const float* H1, const float* dZ2, float* p2, int64_t p2_floats,
                   void* stream) {
-  if (!valid_h(H) || mb <= 0 || net < -1 || net > 1 || S < 1 || !H1 || !dZ2 || !p2) return -1;
-  const int KR = ((mb + S - 1) / S + kDwKC - 1) / kDwKC * kDwKC;
-  if ((int64_t)KR * (S - 1) >= mb) return -1;                    // an empty split: use satrl_ppo_dw2_splits
-  if (!p2_fits(H, net, S, p2_floats, "satrl_ppo_dw2")) return -1;
-  const dim3 g((unsigned)(dw2_tiles(H, net) * S));
-  hipStream_t st = (hipStream_t)stream;
-  if (H == 64)
-    hipLaunchKernelGGL(dw2_kernel<64>, g, dim3(256), 0, st, mb, S, KR, net, H1, dZ2, p2);
-  else if (H == 128)
-    hipLaunchKernelGGL(dw2_kernel<128>, g, dim3(256), 0, st, mb, S, KR, net, H1, dZ2, p2);
-  else
-    hipLaunchKernelGGL(dw2_kernel<256>, g, dim3(256), 0, st, mb, S, KR, net, H1, dZ2, p2);
-  LAUNCH_CHECK();
-  return 0;
+  if (int rc = refuse(__func__, H, kAnyH, mb, "mb", net, SATRL_PTRS(H1, dZ2, p2))) return rc;
+  int KR = 0;
+  if (int rc = split_size(__func__, S, mb, kDwKC, "satrl_ppo_dw2_splits", &KR)) return rc;
+  if (int rc = p2_fits(__func__, H, net, S, p2_floats)) return rc;
+  const char* who = __func__;
+  return with_width<kNW256>(H, [&](auto w) {                      // (dw2_kernel takes the width alone)
+    return launch(who, dw2_kernel<decltype(w)::H>, dw2_tiles(H, net) * S, 256, stream, mb, S, KR, net, H1, dZ2, p2);
+  });
 }
 
 int satrl_ppo_reduce(int H, int mb, int net, int S, int mode, const float* p2, int64_t p2_floats, const float* p1,
@@ -3584,48 +3606,56 @@ int satrl_ppo_reduce(int H, int mb, int net, int S, int mode, const float* p2, i
   // mode bit 4: the W2 region only (satrl_ppo_dw2_kx_w1 summed the others)
   const bool w2_only = (mode & 4) != 0;
   mode &= 3;
-  if (!valid_h(H) || mb <= 0 || net < -1 || net > 1 || S < 1 || mode < 1 || !G || (w2_only && !(mode & 1)))
-    return -1;
-  if ((mode & 1) && (!p2 || (!w2_only && (!p1 || !pt)))) return -1;
-  if ((mode & 1) && !p2_fits(H, net, S, p2_floats, "satrl_ppo_reduce")) return -1;   // the slabs it reads
-  if ((mode & 2) && (!nsq || !steps)) return -1;
+  if (int rc = refuse(__func__, H, kAnyH, mb, "mb", net, SATRL_PTRS(G))) return rc;
+  if (S < 1) return fail(-1, __func__, "S " + to_string(S) + " < 1");
+  if (mode < 1 || (w2_only && !(mode & 1))) return fail(-1, __func__, "mode has no bit 1 or 2, or bit 4 without 1");
+  if (mode & 1) {
+    if (int rc = w2_only ? null_arg(__func__, SATRL_PTRS(p2)) : null_arg(__func__, SATRL_PTRS(p2, p1, pt))) return rc;
+    if (int rc = p2_fits(__func__, H, net, S, p2_floats)) return rc;   // the slabs it reads
+  }
+  if (mode & 2)
+    if (int rc = null_arg(__func__, SATRL_PTRS(nsq, steps))) return rc;
   const RedGeom g = geom(H, mb, S, net);
   const int nb = w2_only ? g.nb2 : n_blocks(g);
   unsigned long long* sp = satrl_span::take(satrl_span::kReduce, (int64_t)nb * 4);
   launch_span(reduce_kernel<true>, reduce_kernel<false>, sp, dim3(nb), dim3(256), stream, H, mode, g.nb2, g.S,
               g.net, g.ch2, p2, steps, G, nsq, g, p1, pt, 1);
-  LAUNCH_CHECK();
-  return 0;
+  return launched(__func__);
 }
 
 int satrl_ppo_reduce_dp(int H, int mb, int net, int world, float* G, double* nsq, double* steps, void* stream) {
-  if (!valid_h(H) || mb <= 0 || net < -1 || net > 1 || world < 1 || !G || !nsq || !steps) return -1;
+  if (int rc = refuse(__func__, H, kAnyH, mb, "mb", net, SATRL_PTRS(G, nsq, steps))) return rc;
+  if (world < 1) return fail(-1, __func__, "world " + to_string(world) + " < 1");
   const RedGeom g = geom(H, mb, 1, net);
-  hipLaunchKernelGGL(reduce_kernel<false>, dim3(n_blocks(g)), dim3(256), 0, (hipStream_t)stream, H, 2, g.nb2, g.S,
-                     g.net, g.ch2, nullptr, steps, G, nsq, g, nullptr, nullptr, world, nullptr);
-  LAUNCH_CHECK();
-  return 0;
+  return launch(__func__, reduce_kernel<false>, n_blocks(g), 256, stream, H, 2, g.nb2, g.S, g.net, g.ch2, nullptr,
+                steps, G, nsq, g, nullptr, nullptr, world, nullptr);
+}
+
+// a failed HIP call of `who` (not a launch): -2 with what was attempted and HIP's text
+static int hip_failed(const char* who, const char* what) {
+  return fail(-2, who, std::string(what) + " failed: " + hipGetErrorString(hipGetLastError()));
 }
 
 int satrl_peer_buffer_bytes(int64_t n, int world, int64_t* bytes) {
-  if (n <= 0 || world < 1 || world > kPeerMaxW || !bytes) return -1;
+  if (n <= 0) return fail(-1, __func__, "n " + to_string(n) + " <= 0");
+  if (int rc = outside(__func__, "world", world, 1, kPeerMaxW)) return rc;
+  if (int rc = null_arg(__func__, SATRL_PTRS(bytes))) return rc;
   *bytes = peer_bytes(n, world);
   return 0;
 }
 
 int satrl_peer_alloc(int64_t bytes, void** buf, void* ipc_handle) {
-  if (bytes <= 0 || !buf || !ipc_handle) return -1;
+  if (bytes <= 0) return fail(-1, __func__, "bytes " + to_string(bytes) + " <= 0");
+  if (int rc = null_arg(__func__, SATRL_PTRS(buf, ipc_handle))) return rc;
   void* p = nullptr;
-  if (hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocUncached) != hipSuccess) {
-    g_err = "satrl_peer_alloc: hipExtMallocWithFlags(uncached) failed";
-    return -2;
-  }
+  if (hipExtMallocWithFlags(&p, (size_t)bytes, hipDeviceMallocUncached) != hipSuccess)
+    return hip_failed(__func__, "hipExtMallocWithFlags(uncached)");
   hipIpcMemHandle_t h;
   if (hipMemset(p, 0, (size_t)bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
       hipIpcGetMemHandle(&h, p) != hipSuccess) {
+    const int rc = hip_failed(__func__, "zeroing / hipIpcGetMemHandle");
     (void)hipFree(p);
-    g_err = "satrl_peer_alloc: zeroing / hipIpcGetMemHandle failed";
-    return -2;
+    return rc;
   }
   std::memcpy(ipc_handle, &h, sizeof(h));
   *buf = p;
@@ -3633,191 +3663,150 @@ int satrl_peer_alloc(int64_t bytes, void** buf, void* ipc_handle) {
 }
 
 int satrl_peer_open(const void* ipc_handle, void** buf) {
-  if (!ipc_handle || !buf) return -1;
+  if (int rc = null_arg(__func__, SATRL_PTRS(ipc_handle, buf))) return rc;
   hipIpcMemHandle_t h;
   std::memcpy(&h, ipc_handle, sizeof(h));
-  if (hipIpcOpenMemHandle(buf, h, hipIpcMemLazyEnablePeerAccess) != hipSuccess) {
-    g_err = "satrl_peer_open: hipIpcOpenMemHandle failed";
-    return -2;
-  }
+  if (hipIpcOpenMemHandle(buf, h, hipIpcMemLazyEnablePeerAccess) != hipSuccess)
+    return hip_failed(__func__, "hipIpcOpenMemHandle");
   return 0;
 }
 
-int satrl_peer_close(void* buf) { return buf && hipIpcCloseMemHandle(buf) == hipSuccess ? 0 : -2; }
-int satrl_peer_free(void* buf) { return buf && hipFree(buf) == hipSuccess ? 0 : -2; }
+int satrl_peer_close(void* buf) {
+  if (!buf) return fail(-2, __func__, "buf is NULL");
+  return hipIpcCloseMemHandle(buf) == hipSuccess ? 0 : hip_failed(__func__, "hipIpcCloseMemHandle");
+}
+int satrl_peer_free(void* buf) {
+  if (!buf) return fail(-2, __func__, "buf is NULL");
+  return hipFree(buf) == hipSuccess ? 0 : hip_failed(__func__, "hipFree");
+}
 
 int satrl_peer_error(const void* buf, uint64_t* err, void* stream) {
-  if (!buf || !err) return -1;
+  if (int rc = null_arg(__func__, SATRL_PTRS(buf, err))) return rc;
   hipStream_t st = (hipStream_t)stream;               // ordered after the calls queued on `stream`
-  return hipMemcpyAsync(err, static_cast<const char*>(buf) + 4 * kPeerMaxBlocks, 8, hipMemcpyDeviceToHost, st) ==
-                     hipSuccess &&
-                 hipStreamSynchronize(st) == hipSuccess
-             ? 0
-             : -2;
+  const char* word = static_cast<const char*>(buf) + 4 * kPeerMaxBlocks;
+  if (hipMemcpyAsync(err, word, 8, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess)
+    return 0;
+  return hip_failed(__func__, "reading the error word");
 }
 
 int satrl_peer_reset(void* buf, int64_t bytes, void* stream) {
-  if (!buf || bytes < kPeerHdr) return -1;
+  if (int rc = null_arg(__func__, SATRL_PTRS(buf))) return rc;
+  if (bytes < kPeerHdr)
+    return fail(-1, __func__, to_string(bytes) + " bytes are smaller than the header, " + to_string(kPeerHdr));
   hipStream_t st = (hipStream_t)stream;
-  return hipMemsetAsync(buf, 0, (size_t)bytes, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess ? 0 : -2;
+  if (hipMemsetAsync(buf, 0, (size_t)bytes, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess) return 0;
+  return hip_failed(__func__, "zeroing the buffer");
 }
 
 // the peer kernel's grid at width H: reduce_dp's block count, capped at one
 // block per CU of the current device and at what can be resident at once
 int satrl_peer_blocks(int H, int* blocks) {
-  if (!valid_h(H) || !blocks) return -1;
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, peer_allreduce_kernel, 256, 0) != hipSuccess) {
-    g_err = "satrl_peer_blocks: device query failed";
-    return -2;
-  }
-  const int nb = n_blocks(geom(H, 1, 1, -1));
-  *blocks = std::min(nb, std::min(cus, cus * per_cu));
-  return *blocks > 0 ? 0 : -2;
+  if (int rc = refuse(__func__, H, kAnyH, 1, "", 0, SATRL_PTRS(blocks))) return rc;
+  Residency r;
+  if (!residency(peer_allreduce_kernel, 256, &r)) return hip_failed(__func__, "the device query");
+  *blocks = std::min(n_blocks(geom(H, 1, 1, -1)), std::min(r.cus, r.blocks()));
+  return *blocks > 0 ? 0 : fail(-2, __func__, "no block of the peer kernel can be resident");
 }
 
 int satrl_ppo_allreduce_peer(int H, int mb, int world, int rank, void* const* bufs, float* G, double* nsq,
                              double* steps, int blocks, double timeout_s, void* stream) {
-  if (!valid_h(H) || mb <= 0 || world < 1 || world > kPeerMaxW || rank < 0 || rank >= world || !bufs || !G || !nsq ||
-      !steps || blocks < 1 || blocks > kPeerMaxBlocks || !(timeout_s > 0.0) || timeout_s > 1e7)
-    return -1;
+  if (int rc = refuse(__func__, H, kAnyH, mb, "mb", 0)) return rc;
+  if (int rc = outside(__func__, "world", world, 1, kPeerMaxW)) return rc;
+  if (int rc = outside(__func__, "rank", rank, 0, world - 1)) return rc;
+  if (int rc = null_arg(__func__, SATRL_PTRS(bufs, G, nsq, steps))) return rc;
+  if (int rc = outside(__func__, "blocks", blocks, 1, kPeerMaxBlocks)) return rc;
+  if (!(timeout_s > 0.0) || timeout_s > 1e7) return fail(-1, __func__, "timeout_s is not in (0, 1e7]: no deadline");
   PeerBufs pb{};
   for (int j = 0; j < world; ++j) {
-    if (!bufs[j]) return -1;
+    if (!bufs[j]) return fail(-1, __func__, "bufs[" + to_string(j) + "] is NULL");
     pb.buf[j] = static_cast<unsigned long long*>(bufs[j]);
   }
   // every block must be resident at once (a block waits on values other blocks push)
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, peer_allreduce_kernel, 256, 0) != hipSuccess) {
-    g_err = "satrl_ppo_allreduce_peer: device query failed";
-    return -2;
-  }
-  if (blocks > cus * per_cu) {
-    g_err = "satrl_ppo_allreduce_peer: " + std::to_string(blocks) + " blocks cannot all be resident (" +
-            std::to_string(cus) + " CUs x " + std::to_string(per_cu) + ")";
-    return -1;
-  }
+  Residency r;
+  if (!residency(peer_allreduce_kernel, 256, &r)) return hip_failed(__func__, "the device query");
+  if (blocks > r.blocks())
+    return fail(-1, __func__, to_string(blocks) + " blocks cannot all be resident (" + to_string(r.cus) +
+                             " CUs x " + to_string(r.per_cu) + ")");
   const RedGeom g = geom(H, mb, 1, -1);
   const unsigned long long ticks = (unsigned long long)(timeout_s * 1e8);   // s_memrealtime: 100 MHz
-  hipLaunchKernelGGL(peer_allreduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, H, g, world, rank, pb, G,
-                     nsq, steps, ticks);
-  LAUNCH_CHECK();
-  return 0;
+  return launch(__func__, peer_allreduce_kernel, blocks, 256, stream, H, g, world, rank, pb, G, nsq, steps, ticks);
 }
 
 int satrl_ppo_adam(int H, int mb, int net, const double* nsq, const double* steps, const double* bct, int bct_len,
                    const float* lr, float beta1, float beta2, float eps, float max_norm, int use_clip, const float* G,
                    float* P, float* M, float* V, void* W2X, void* stream) {
-  if (!valid_h(H) || mb <= 0 || net < -1 || net > 1 || !nsq || !steps || !bct || bct_len < 1 || !lr || !G || !P ||
-      !M || !V)
-    return -1;
+  if (int rc = refuse(__func__, H, kAnyH, mb, "mb", net, SATRL_PTRS(nsq, steps, bct, lr, G, P, M, V))) return rc;
+  if (bct_len < 1) return fail(-1, __func__, "bct_len " + to_string(bct_len) + " < 1");
   const int nblk = n_blocks(geom(H, mb, 1, net));
   unsigned long long* sp = satrl_span::take(satrl_span::kAdam, (int64_t)n_adam_blocks(H, net) * 4);
   launch_span(adam_kernel<true>, adam_kernel<false>, sp, dim3(n_adam_blocks(H, net)), dim3(256), stream, H, nblk, nsq,
               G, P, M, V, net, bct_len, steps, bct, lr, beta1, beta2, eps, max_norm, use_clip, W2X);
-  LAUNCH_CHECK();
-  return 0;
+  return launched(__func__);
 }
 
-int64_t satrl_ppo_w2x_floats(int H) { return valid_h(H) ? w2x_floats(H) : -1; }
+int64_t satrl_ppo_w2x_floats(int H) {
+  return refuse(__func__, H, kAnyH, 1, "", 0) ? -1 : w2x_floats(H);
+}
 
 int satrl_ppo_w2x_sync(int H, int net, const float* P, void* W2X, void* stream) {
-  if (!valid_h(H) || net < -1 || net > 1 || !P || !W2X) return -1;
+  if (int rc = refuse(__func__, H, kAnyH, 1, "", net, SATRL_PTRS(P, W2X))) return rc;
   const int ntc = H / 32;
-  hipLaunchKernelGGL(w2x_sync_kernel, dim3((net < 0 ? 2 : 1) * ntc * ntc), dim3(256), 0, (hipStream_t)stream, H, net,
-                     P, W2X);
-  LAUNCH_CHECK();
-  return 0;
+  return launch(__func__, w2x_sync_kernel, (net < 0 ? 2 : 1) * ntc * ntc, 256, stream, H, net, P, W2X);
 }
 
 int satrl_ppo_stage(int64_t rows, const float* src, const int64_t* perm, const int64_t* group, float* stage,
                     void* stream) {
-  if (rows <= 0 || !src || !perm || !group || !stage) return -1;
-  hipLaunchKernelGGL(stage_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows,
-                     reinterpret_cast<const float4*>(src), perm, group, reinterpret_cast<float4*>(stage));
-  LAUNCH_CHECK();
-  return 0;
+  if (rows <= 0) return fail(-1, __func__, "rows " + to_string(rows) + " <= 0");
+  if (int rc = null_arg(__func__, SATRL_PTRS(src, perm, group, stage))) return rc;
+  return launch(__func__, stage_kernel, (rows * 8 + 255) / 256, 256, stream, rows,
+                reinterpret_cast<const float4*>(src), perm, group, reinterpret_cast<float4*>(stage));
 }
 
 int satrl_ppo_group_advance(int64_t* group, void* stream) {
-  if (!group) return -1;
-  hipLaunchKernelGGL(group_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, group);
-  LAUNCH_CHECK();
-  return 0;
+  if (int rc = null_arg(__func__, SATRL_PTRS(group))) return rc;
+  return launch(__func__, group_advance_kernel, 1, 1, stream, group);
 }
 
 int satrl_policy_act(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
                      uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act0,
                      float* logp0, float* act1, float* logp1, void* stream) {
-  if (!valid_h(H) || N <= 0 || !obs || !P0 || !act0 || !logp0) return -1;
-  if (P1 && (!act1 || !logp1)) return -1;
+  if (int rc = refuse(__func__, H, kAnyH, N, "N", 0, SATRL_PTRS(obs, P0, act0, logp0))) return rc;
+  if (P1)                                                          // a second agent brings its outputs
+    if (int rc = null_arg(__func__, SATRL_PTRS(act1, logp1))) return rc;
   const int nag = P1 ? 2 : 1;
-  uint32_t k00, k01, k10, k11;
-  philox_key(seed, 0, k00, k01);
-  philox_key(seed, 1, k10, k11);
-  launch_policy<0>(H, satrl_span::kPolicyAct, dim3((unsigned)(nag * ((N + kPolRows - 1) / kPolRows))), stream, N, obs,
-                   P0, P1, nag, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, logp0, act1, logp1,
-                   nullptr, 0);
-  LAUNCH_CHECK();
-  return 0;
+  const PolicyKeys k(seed);
+  return launch_policy<0>(__func__, H, satrl_span::kPolicyAct, nag, N, stream, obs, P0, P1, nag, max_action, k.k00,
+                          k.k01, k.k10, k.k11, env_offset, step, step_base, act0, logp0, act1, logp1, nullptr, 0);
 }
 
 int satrl_policy_act_pool(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
                           uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act0,
                           float* logp0, float* act1, float* logp1, int pool_agent, const float* pool,
                           int64_t pool_stride, int K, const int32_t* member, void* stream) {
-  const char* why = nullptr;
-  if (!valid_h(H) || N <= 0 || !obs || !P0 || !act0 || !logp0)
-    why = "H not 64/128/256, N <= 0, or a NULL obs, P0, act0 or logp0";
-  else if (!P1 || !act1 || !logp1)
-    why = "both agents are required: a NULL P1, act1 or logp1";
-  else if (pool_agent != 0 && pool_agent != 1)
-    why = "pool_agent is 0 or 1";
-  else if (!pool || !member)
-    why = "a NULL pool or member";
-  else if (K <= 0)
-    why = "K <= 0";
-  else if (pool_stride < layout(H).total || pool_stride % 4 != 0)
-    why = "pool_stride below the layout total or not a multiple of 4";
-  else if (reinterpret_cast<uintptr_t>(pool) & 15)
-    why = "pool is not 16-byte aligned";
-  if (why) {
-    g_err = std::string("satrl_policy_act_pool: ") + why;
-    return -1;
-  }
-  uint32_t k00, k01, k10, k11;
-  philox_key(seed, 0, k00, k01);
-  philox_key(seed, 1, k10, k11);
-  const dim3 g((unsigned)(2 * ((N + kPolRows - 1) / kPolRows)));
-  hipStream_t s = (hipStream_t)stream;
+  if (int rc = refuse(__func__, H, kAnyH, N, "N", 0, SATRL_PTRS(obs, P0, act0, logp0))) return rc;
+  if (!P1 || !act1 || !logp1) return fail(-1, __func__, "both agents are required: a NULL P1, act1 or logp1");
+  if (pool_agent != 0 && pool_agent != 1) return fail(-1, __func__, "pool_agent is 0 or 1");
+  if (int rc = null_arg(__func__, SATRL_PTRS(pool, member))) return rc;
+  if (K <= 0) return fail(-1, __func__, "K <= 0");
+  if (pool_stride < layout(H).total || pool_stride % 4 != 0)
+    return fail(-1, __func__, "pool_stride below the layout total or not a multiple of 4");
+  if (reinterpret_cast<uintptr_t>(pool) & 15) return fail(-1, __func__, "pool is not 16-byte aligned");
+  const PolicyKeys k(seed);
+  const char* who = __func__;
   // (no SPAN form: under a span probe this is the launch, and nothing is logged)
-  if (H == 64)
-    hipLaunchKernelGGL((policy_pool_kernel<64, 4>), g, dim3(256), 0, s, N, obs, pool, member, pool_stride, K,
-                       pool_agent, P0, P1, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, logp0,
-                       act1, logp1);
-  else if (H == 128)
-    hipLaunchKernelGGL((policy_pool_kernel<128, 8>), g, dim3(512), 0, s, N, obs, pool, member, pool_stride, K,
-                       pool_agent, P0, P1, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, logp0,
-                       act1, logp1);
-  else
-    hipLaunchKernelGGL((policy_pool_kernel<256, kPolNW>), g, dim3(kPolNW * 64), 0, s, N, obs, pool, member,
-                       pool_stride, K, pool_agent, P0, P1, max_action, k00, k01, k10, k11, env_offset, step,
-                       step_base, act0, logp0, act1, logp1);
-  LAUNCH_CHECK();
-  return 0;
+  return with_width<kPolNW>(H, [&](auto w) {
+    using W = decltype(w);
+    return launch(who, policy_pool_kernel<W::H, W::NW>, 2 * ((N + kPolRows - 1) / kPolRows), W::NW * 64, stream, N, obs,
+                  pool, member, pool_stride, K, pool_agent, P0, P1, max_action, k.k00, k.k01, k.k10, k.k11, env_offset,
+                  step, step_base, act0, logp0, act1, logp1);
+  });
 }
 
 int satrl_opponent_assign(uint64_t seed, uint64_t iteration, int64_t first_block, int64_t n_blocks, int filled,
                           double latest_prob, int32_t* member_out) {
-  if (!member_out || n_blocks <= 0 || first_block < 0 || filled < 0 || !(latest_prob >= 0.0 && latest_prob <= 1.0)) {
-    g_err = "satrl_opponent_assign: a NULL output, n_blocks <= 0, first_block < 0, filled < 0, or latest_prob "
-            "outside [0, 1]";
-    return -1;
-  }
+  if (!member_out || n_blocks <= 0 || first_block < 0 || filled < 0 || !(latest_prob >= 0.0 && latest_prob <= 1.0))
+    return fail(-1, __func__,
+                "a NULL output, n_blocks <= 0, first_block < 0, filled < 0, or latest_prob outside [0, 1]");
   uint32_t k0, k1;
   philox_key(seed, 3, k0, k1);
   for (int64_t i = 0; i < n_blocks; ++i) {
@@ -3833,36 +3822,29 @@ int satrl_opponent_assign(uint64_t seed, uint64_t iteration, int64_t first_block
 int satrl_policy_eval(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
                       int det_mask, uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base,
                       float* act0, float* act1, void* stream) {
-  if (!valid_h(H) || N <= 0 || !obs || !P0 || !act0) return -1;
-  if (det_mask < 0 || det_mask > 3 || ((det_mask & 2) && !P1)) return -1;
-  if (P1 && !act1) return -1;
+  if (int rc = refuse(__func__, H, kAnyH, N, "N", 0, SATRL_PTRS(obs, P0, act0))) return rc;
+  if (det_mask < 0 || det_mask > 3 || ((det_mask & 2) && !P1))
+    return fail(-1, __func__, "det_mask " + to_string(det_mask) + " is outside 0 .. 3, or has bit 2 without P1");
+  if (P1 && !act1) return fail(-1, __func__, "act1 is NULL");
   const int nag = P1 ? 2 : 1;
-  uint32_t k00, k01, k10, k11;
-  philox_key(seed, 0, k00, k01);
-  philox_key(seed, 1, k10, k11);
-  launch_policy<2>(H, satrl_span::kPolicyAct, dim3((unsigned)(nag * ((N + kPolRows - 1) / kPolRows))), stream, N, obs,
-                   P0, P1, nag, max_action, k00, k01, k10, k11, env_offset, step, step_base, act0, nullptr, act1,
-                   nullptr, nullptr, det_mask);
-  LAUNCH_CHECK();
-  return 0;
+  const PolicyKeys k(seed);
+  return launch_policy<2>(__func__, H, satrl_span::kPolicyAct, nag, N, stream, obs, P0, P1, nag, max_action, k.k00,
+                          k.k01, k.k10, k.k11, env_offset, step, step_base, act0, nullptr, act1, nullptr, nullptr,
+                          det_mask);
 }
 
 int satrl_scripted_act(int64_t N, const float* obs, const satrl_scripted_law* law, float* act, void* stream) {
-  if (N <= 0 || !obs || !law || !act) {
-    g_err = "satrl_scripted_act: N <= 0, or a NULL obs, law or act";
-    return -1;
-  }
-  hipLaunchKernelGGL(scripted_kernel, dim3((unsigned)((N + kScriptedBlock - 1) / kScriptedBlock)),
-                     dim3(kScriptedBlock), 0, (hipStream_t)stream, N, obs, law, act);
-  LAUNCH_CHECK();
-  return 0;
+  if (N <= 0) return fail(-1, __func__, "N " + to_string(N) + " <= 0");
+  if (int rc = null_arg(__func__, SATRL_PTRS(obs, law, act))) return rc;
+  return launch(__func__, scripted_kernel, (N + kScriptedBlock - 1) / kScriptedBlock, kScriptedBlock, stream, N, obs,
+                law, act);
 }
 
 int satrl_policy_act_scripted(int H, int64_t N, const float* obs, const float* obs_law, const float* P, int agent,
                               float max_action, uint64_t seed, int64_t env_offset, uint64_t step,
                               const uint64_t* step_base, float* act, float* logp, const satrl_scripted_law* law,
                               float* act_scripted, void* stream) {
-  return launch_policy_scripted<0>("satrl_policy_act_scripted", H, N, obs, obs_law, P, agent, max_action, 0, seed,
+  return launch_policy_scripted<0>(__func__, H, N, obs, obs_law, P, agent, max_action, 0, seed,
                                    env_offset, step, step_base, act, logp, law, act_scripted, stream);
 }
 
@@ -3870,84 +3852,74 @@ int satrl_policy_eval_scripted(int H, int64_t N, const float* obs, const float* 
                                float max_action, int det, uint64_t seed, int64_t env_offset, uint64_t step,
                                const uint64_t* step_base, float* act, const satrl_scripted_law* law,
                                float* act_scripted, void* stream) {
-  return launch_policy_scripted<2>("satrl_policy_eval_scripted", H, N, obs, obs_law, P, agent, max_action, det, seed,
+  return launch_policy_scripted<2>(__func__, H, N, obs, obs_law, P, agent, max_action, det, seed,
                                    env_offset, step, step_base, act, nullptr, law, act_scripted, stream);
 }
 
 int satrl_policy_value(int H, int64_t N, const float* obs, const float* P, float* v_out, void* stream) {
-  if (!valid_h(H) || N <= 0 || !obs || !P || !v_out) return -1;
-  launch_policy<1>(H, satrl_span::kPolicyValue, dim3((unsigned)((N + kPolRows - 1) / kPolRows)), stream, N, obs, P,
-                   nullptr, 1, 0.0f, 0u, 0u, 0u, 0u, (int64_t)0, (uint64_t)0, nullptr, nullptr, nullptr, nullptr,
-                   nullptr, v_out, 0);
-  LAUNCH_CHECK();
-  return 0;
+  if (int rc = refuse(__func__, H, kAnyH, N, "N", 0, SATRL_PTRS(obs, P, v_out))) return rc;
+  return launch_policy<1>(__func__, H, satrl_span::kPolicyValue, 1, N, stream, obs, P, nullptr, 1, 0.0f, 0u, 0u, 0u, 0u,
+                          (int64_t)0, (uint64_t)0, nullptr, nullptr, nullptr, nullptr, nullptr, v_out, 0);
 }
 
 // f64 elements of satrl_ppo_diagnostics' scratch: a line per 32-row block, and
 // above kDiagChunk blocks a line per chunk of them (the first reduce level)
-int64_t satrl_ppo_diagnostics_scratch(int64_t n) {
-  if (n <= 0 || n > (int64_t)0x7FFFFFFF - 2 * kPolRows) return -1;
+static int64_t diag_scratch(const char* who, int64_t n) {
+  if (n <= 0 || n > (int64_t)0x7FFFFFFF - 2 * kPolRows)
+    return fail(-1, who, "n " + to_string(n) + " is empty (<= 0) or above what 32 bits index");
   const int64_t nrb = (n + kPolRows - 1) / kPolRows;
   return kDiagLine * (nrb + (nrb > kDiagChunk ? (nrb + kDiagChunk - 1) / kDiagChunk : 0));
 }
+int64_t satrl_ppo_diagnostics_scratch(int64_t n) { return diag_scratch(__func__, n); }
 
 int satrl_ppo_diagnostics(int H, int64_t n, const float* src, const int64_t* idx, const float* P, float epsilon,
                           float max_action, double* sums, double* scratch, int64_t scratch_len, float* rows_out,
                           void* stream) {
-  const int64_t need = satrl_ppo_diagnostics_scratch(n);
-  if (!valid_h(H) || need < 0 || !src || !P || !sums || !scratch || scratch_len < need) {
-    g_err = "satrl_ppo_diagnostics: H " + std::to_string(H) + ", n " + std::to_string(n) + ", scratch " +
-            std::to_string(scratch_len) + " of " + std::to_string(need) + " f64, or a NULL src / P / sums / scratch";
-    return -1;
-  }
+  if (int rc = refuse(__func__, H, kAnyH, n, "n", 0, SATRL_PTRS(src, P, sums, scratch))) return rc;
+  const int64_t need = diag_scratch(__func__, n);
+  if (need < 0) return -1;
+  if (scratch_len < need)
+    return fail(-1, __func__, "scratch holds " + to_string(scratch_len) + " f64, n " + to_string(n) + " needs " +
+                             to_string(need));
   const int64_t nrb = (n + kPolRows - 1) / kPolRows;
-  const dim3 g((unsigned)(2 * nrb));
-  hipStream_t s = (hipStream_t)stream;
-  if (H == 64)
-    hipLaunchKernelGGL((diag_kernel<64, 4>), g, dim3(256), 0, s, (int)n, src, idx, P, epsilon, max_action, scratch,
-                       rows_out);
-  else if (H == 128)
-    hipLaunchKernelGGL((diag_kernel<128, 8>), g, dim3(512), 0, s, (int)n, src, idx, P, epsilon, max_action, scratch,
-                       rows_out);
-  else
-    hipLaunchKernelGGL((diag_kernel<256, kPolNW>), g, dim3(kPolNW * 64), 0, s, (int)n, src, idx, P, epsilon,
-                       max_action, scratch, rows_out);
-  LAUNCH_CHECK();
+  const char* who = __func__;
+  if (int rc = with_width<kPolNW>(H, [&](auto w) {
+        using W = decltype(w);
+        return launch(who, diag_kernel<W::H, W::NW>, 2 * nrb, W::NW * 64, stream, (int)n, src, idx, P, epsilon,
+                      max_action, scratch, rows_out);
+      }))
+    return rc;
   const double* lines = scratch;
   int64_t nl = nrb;
   if (nrb > kDiagChunk) {                                          // first level: a line per chunk of blocks
     double* l1 = scratch + nrb * kDiagLine;
     nl = (nrb + kDiagChunk - 1) / kDiagChunk;
-    hipLaunchKernelGGL(diag_reduce_kernel, dim3((unsigned)nl), dim3(1024), 0, s, lines, nrb, kDiagChunk, l1, 0);
-    LAUNCH_CHECK();
+    if (int rc = launch(who, diag_reduce_kernel, nl, 1024, stream, lines, nrb, kDiagChunk, l1, 0)) return rc;
     lines = l1;
   }
-  hipLaunchKernelGGL(diag_reduce_kernel, dim3(1), dim3(1024), 0, s, lines, nl, (int)nl, sums, 1);
-  LAUNCH_CHECK();
-  return 0;
+  return launch(who, diag_reduce_kernel, 1, 1024, stream, lines, nl, (int)nl, sums, 1);
 }
 
 int satrl_ppo_tanh(int64_t n, const float* x, float* y, void* stream) {
-  if (n <= 0 || n > (int64_t)256 * 0x7FFFFFFF || !x || !y) return -1;
-  hipLaunchKernelGGL(tanh_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, x, y);
-  LAUNCH_CHECK();
-  return 0;
+  if (n <= 0) return fail(-1, __func__, "n " + to_string(n) + " <= 0");
+  if (int rc = null_arg(__func__, SATRL_PTRS(x, y))) return rc;
+  return launch(__func__, tanh_kernel, (n + 255) / 256, 256, stream, n, x, y);
 }
 
 int satrl_tanh_forms(const float* x, float* y, int64_t n, int form, void* stream) {
-  if (n <= 0 || n % 8 != 0 || n / 8 > (int64_t)256 * 0x7FFFFFFF || !x || !y || form < 0 || form > 1) return -1;
+  if (n <= 0 || n % 8 != 0) return fail(-1, __func__, "n " + to_string(n) + " is not a positive multiple of 8");
+  if (int rc = null_arg(__func__, SATRL_PTRS(x, y))) return rc;
+  if (int rc = outside(__func__, "form", form, 0, 1)) return rc;
   const int64_t n8 = n / 8;
-  const dim3 g((unsigned)((n8 + 255) / 256));
-  if (form == 0) hipLaunchKernelGGL(tanh_forms_kernel<0>, g, dim3(256), 0, (hipStream_t)stream, n8, x, y);
-  else hipLaunchKernelGGL(tanh_forms_kernel<1>, g, dim3(256), 0, (hipStream_t)stream, n8, x, y);
-  LAUNCH_CHECK();
-  return 0;
+  return launch(__func__, form == 0 ? tanh_forms_kernel<0> : tanh_forms_kernel<1>, (n8 + 255) / 256, 256, stream, n8, x,
+                y);
 }
 
 // live launch spans (span_probe.h): the probe buffer, its bump pointer and
 // the launch log, host state of the library (one probe per process)
 int satrl_span_probe(void* buf, int64_t bytes, void* stream) {
-  if ((buf == nullptr) != (bytes == 0) || bytes < 0) return -1;
+  if ((buf == nullptr) != (bytes == 0) || bytes < 0)
+    return fail(-1, __func__, "a buffer without bytes, bytes without a buffer, or bytes < 0");
   g_span.buf = static_cast<unsigned long long*>(buf);
   g_span.words = bytes / 8;
   if (!buf) return 0;                                              // stop: the log stays readable
@@ -3955,8 +3927,7 @@ int satrl_span_probe(void* buf, int64_t bytes, void* stream) {
   g_span.log.clear();
   if (hipMemsetAsync(buf, 0, (size_t)bytes, (hipStream_t)stream) != hipSuccess) {
     g_span = SpanState{};
-    g_err = "satrl_span_probe: hipMemsetAsync failed";
-    return -2;
+    return hip_failed(__func__, "hipMemsetAsync");
   }
   return 0;
 }
@@ -3964,14 +3935,16 @@ int satrl_span_probe(void* buf, int64_t bytes, void* stream) {
 int64_t satrl_span_probe_launches(void) { return (int64_t)g_span.log.size(); }
 
 int satrl_span_probe_launch(int64_t i, int* kind, int64_t* word_offset, int64_t* waves) {
-  if (i < 0 || i >= (int64_t)g_span.log.size() || !kind || !word_offset || !waves) return -1;
+  if (i < 0 || i >= (int64_t)g_span.log.size())
+    return fail(-1, __func__, "launch " + to_string(i) + " of " + to_string(g_span.log.size()) + " logged");
+  if (int rc = null_arg(__func__, SATRL_PTRS(kind, word_offset, waves))) return rc;
   *kind = g_span.log[(size_t)i].kind;
   *word_offset = g_span.log[(size_t)i].off;
   *waves = g_span.log[(size_t)i].waves;
   return 0;
 }
 
-const char* satrl_ppo_last_error(void) { return g_err.c_str(); }
+const char* satrl_ppo_last_error(void) { return satrl_err::slot.c_str(); }
 
 }  // extern "C"
 

@@ -1,20 +1,14 @@
 // rollout_kernels.hip -- gfx950 kernels behind include/satrl_rollout.h.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 
 #include "philox_device.h"
+#include "satrl_error.h"
 #include "satrl_rollout.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-#define HIP_CHECK_LAUNCH()                                                   \
-  do {                                                                       \
-    hipError_t e_ = hipGetLastError();                                       \
-    if (e_ != hipSuccess) { g_err = hipGetErrorString(e_); return -2; }      \
-  } while (0)
 
 // ---------------------------------------------------------------------------
 // GAE reverse scan (ppo_continuous.py:201-208), one lane per env.  The time
@@ -338,9 +332,18 @@ __global__ void __launch_bounds__(64) episode_record_kernel(int64_t N, const dou
   if (m != 0ull && threadIdx.x == 0) atomicSub(alive, (int32_t)__popcll(m));
 }
 
-int fail(const char* what) {
-  g_err = what;
-  return -1;
+using satrl_err::fail;
+using satrl_err::launch;
+using satrl_err::null_arg;
+
+// an entry point's count (T or N) under its own name
+int positive(const char* who, const char* name, int64_t n) {
+  return n > 0 ? 0 : fail(-1, who, std::string(name) + " must be positive");
+}
+// the 2 x blocks doubles of satrl_moments_ordered's scratch
+int64_t moments_scratch(const char* who, int64_t n) {
+  if (positive(who, "n", n)) return -1;
+  return 2 * std::min<int64_t>((n + 255) / 256, 1024);
 }
 
 }  // namespace
@@ -349,116 +352,87 @@ extern "C" {
 
 int satrl_obs_normalize(int64_t N, const float* raw, const float* stats, float clip, float* out, const float* pivot,
                         double* acc, void* stream) {
-  if (N <= 0) return fail("satrl_obs_normalize: N must be positive");
-  if (!raw) return fail("satrl_obs_normalize: raw is NULL");
-  if (!stats) return fail("satrl_obs_normalize: stats is NULL");
-  if (!out) return fail("satrl_obs_normalize: out is NULL");
-  if (raw == out) return fail("satrl_obs_normalize: out must not be raw");
-  if (acc && !pivot) return fail("satrl_obs_normalize: pivot is NULL with a non-NULL acc");
+  if (int rc = positive(__func__, "N", N)) return rc;
+  if (int rc = null_arg(__func__, SATRL_PTRS(raw, stats, out))) return rc;
+  if (raw == out) return fail(-1, __func__, "out must not be raw");
+  if (acc && !pivot) return fail(-1, __func__, "pivot is NULL with a non-NULL acc");
   const int64_t slots = (N + kSlotRows - 1) / kSlotRows;
   // 16-byte lane accesses need both row buffers on a 16-byte boundary (a slot is 2304 bytes)
   const int vec = (((uintptr_t)raw | (uintptr_t)out) & 15) == 0;
-  hipLaunchKernelGGL(obs_normalize_kernel, dim3((unsigned)slots), dim3(64), 0, (hipStream_t)stream, N, raw, stats,
-                     clip, out, pivot, acc, vec);
-  HIP_CHECK_LAUNCH();
-  return 0;
+  return launch(__func__, obs_normalize_kernel, slots, 64, stream, N, raw, stats, clip, out, pivot, acc, vec);
 }
 
 int satrl_return_scan(int64_t T, int64_t N, const float* r, const uint8_t* done, double gamma, double* carry,
                       double* acc, void* stream) {
-  if (T <= 0) return fail("satrl_return_scan: T must be positive");
-  if (N <= 0) return fail("satrl_return_scan: N must be positive");
-  if (!r) return fail("satrl_return_scan: r is NULL");
-  if (!done) return fail("satrl_return_scan: done is NULL");
-  if (!carry) return fail("satrl_return_scan: carry is NULL");
-  if (!acc) return fail("satrl_return_scan: acc is NULL");
-  hipLaunchKernelGGL(return_scan_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, T, N, r,
-                     done, gamma, carry, acc);
-  HIP_CHECK_LAUNCH();
-  return 0;
+  if (int rc = positive(__func__, "T", T)) return rc;
+  if (int rc = positive(__func__, "N", N)) return rc;
+  if (int rc = null_arg(__func__, SATRL_PTRS(r, done, carry, acc))) return rc;
+  return launch(__func__, return_scan_kernel, (N + 63) / 64, 64, stream, T, N, r, done, gamma, carry, acc);
 }
 
 int satrl_episode_record_reset(int64_t N, double* rec_f64, int32_t* rec_i32, int32_t* alive, void* stream) {
-  if (N <= 0) return fail("satrl_episode_record_reset: N must be positive");
-  if (N > INT32_MAX) return fail("satrl_episode_record_reset: *alive is an int32");
-  if (!rec_f64 || !rec_i32 || !alive) return fail("satrl_episode_record_reset: a NULL buffer");
-  hipLaunchKernelGGL(episode_record_reset_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
-                     N, rec_f64, rec_i32, alive);
-  HIP_CHECK_LAUNCH();
-  return 0;
+  if (int rc = positive(__func__, "N", N)) return rc;
+  if (N > INT32_MAX) return fail(-1, __func__, "*alive is an int32");
+  if (int rc = null_arg(__func__, SATRL_PTRS(rec_f64, rec_i32, alive))) return rc;
+  return launch(__func__, episode_record_reset_kernel, (N + 63) / 64, 64, stream, N, rec_f64, rec_i32, alive);
 }
 
 int satrl_episode_record(int64_t N, const double* reward, const uint8_t* done, const double* obs64, const float* pa,
                          const float* ea, double capture_reward, double* rec_f64, int32_t* rec_i32, int32_t* alive,
                          void* stream) {
-  if (N <= 0) return fail("satrl_episode_record: N must be positive");
-  if (!reward || !done || !obs64 || !pa || !ea || !rec_f64 || !rec_i32 || !alive)
-    return fail("satrl_episode_record: a NULL buffer");
-  hipLaunchKernelGGL(episode_record_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, N,
-                     reward, done, obs64, pa, ea, capture_reward, rec_f64, rec_i32, alive);
-  HIP_CHECK_LAUNCH();
-  return 0;
+  if (int rc = positive(__func__, "N", N)) return rc;
+  if (int rc = null_arg(__func__, SATRL_PTRS(reward, done, obs64, pa, ea, rec_f64, rec_i32, alive))) return rc;
+  return launch(__func__, episode_record_kernel, (N + 63) / 64, 64, stream, N, reward, done, obs64, pa, ea,
+                capture_reward, rec_f64, rec_i32, alive);
 }
 
 int satrl_gae(int64_t T, int64_t N, const float* r, const uint8_t* done, const float* v, float gamma, float lamda,
               float* adv_out, float* vtarget_out, void* stream) {
-  if (T <= 0 || N <= 0 || !r || !done || !v || !adv_out || !vtarget_out) return -1;
+  if (int rc = positive(__func__, "T", T)) return rc;
+  if (int rc = positive(__func__, "N", N)) return rc;
+  if (int rc = null_arg(__func__, SATRL_PTRS(r, done, v, adv_out, vtarget_out))) return rc;
   // gamma*lamda is a python float product, rounded to f32 when it meets the
   // np.float32 gae (NEP 50), ppo_continuous.py:205
   const float c = (float)((double)gamma * (double)lamda);
   const int block = 64;   // N = 16384 envs -> 256 single-wave workgroups, one per CU
-  hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((N + block - 1) / block)), dim3(block), 0, (hipStream_t)stream, T,
-                     N, r, done, v, gamma, c, adv_out, vtarget_out);
-  HIP_CHECK_LAUNCH();
-  return 0;
+  return launch(__func__, gae_kernel, (N + block - 1) / block, block, stream, T, N, r, done, v, gamma, c, adv_out,
+                vtarget_out);
 }
 
 int satrl_gaussian_sample(int64_t N, const float* mean, const float* log_std, float max_action, uint64_t seed,
                           uint32_t agent, int64_t env_offset, uint64_t step, const uint64_t* step_base,
                           float* act_out, float* logp_out, void* stream) {
-  if (N <= 0 || !mean || !log_std || !act_out || !logp_out) return -1;
+  if (int rc = positive(__func__, "N", N)) return rc;
+  if (int rc = null_arg(__func__, SATRL_PTRS(mean, log_std, act_out, logp_out))) return rc;
   uint32_t k0, k1;
   philox_key(seed, agent, k0, k1);
-  hipLaunchKernelGGL(gaussian_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N, mean,
-                     log_std, max_action, k0, k1, env_offset, step, step_base, act_out, logp_out);
-  HIP_CHECK_LAUNCH();
-  return 0;
+  return launch(__func__, gaussian_kernel, (N + 255) / 256, 256, stream, N, mean, log_std, max_action, k0, k1,
+                env_offset, step, step_base, act_out, logp_out);
 }
 
 int satrl_moments(int64_t n, const float* x, double* out, void* stream) {
-  if (n <= 0 || !x || !out) return -1;
+  if (int rc = positive(__func__, "n", n)) return rc;
+  if (int rc = null_arg(__func__, SATRL_PTRS(x, out))) return rc;
   int64_t blocks = (n + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(moments_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, x, out);
-  HIP_CHECK_LAUNCH();
-  return 0;
+  return launch(__func__, moments_kernel, blocks, 256, stream, n, x, out);
 }
 
-int64_t satrl_moments_scratch(int64_t n) {
-  if (n <= 0) return -1;
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  return 2 * blocks;
-}
+int64_t satrl_moments_scratch(int64_t n) { return moments_scratch(__func__, n); }
 
 int satrl_moments_ordered(int64_t n, const float* x, double* out, double* scratch, int64_t scratch_elems,
                           void* stream) {
-  if (n <= 0 || !x || !out || !scratch) return -1;
-  const int64_t need = satrl_moments_scratch(n);
-  if (scratch_elems < need) {
-    g_err = "satrl_moments_ordered: scratch holds " + std::to_string(scratch_elems) + " doubles, " +
-            std::to_string(need) + " are needed";
-    return -1;
-  }
+  const int64_t need = moments_scratch(__func__, n);
+  if (need < 0) return -1;
+  if (int rc = null_arg(__func__, SATRL_PTRS(x, out, scratch))) return rc;
+  if (scratch_elems < need)
+    return fail(-1, __func__, "scratch holds " + std::to_string(scratch_elems) + " doubles, " + std::to_string(need) +
+                             " are needed");
   const int blocks = (int)(need / 2);
-  hipLaunchKernelGGL(moments_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, x,
-                     scratch);
-  HIP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(moments_combine_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, blocks, scratch, out);
-  HIP_CHECK_LAUNCH();
-  return 0;
+  if (int rc = launch(__func__, moments_partial_kernel, blocks, 256, stream, n, x, scratch)) return rc;
+  return launch(__func__, moments_combine_kernel, 1, 256, stream, blocks, scratch, out);
 }
 
-const char* satrl_last_error(void) { return g_err.c_str(); }
+const char* satrl_last_error(void) { return satrl_err::slot.c_str(); }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 #include "satenv_cpu.h"
 #include "satenv_device.h"
 #include "satenv_step.h"
+#include "satrl_error.h"       // satrl_scripted_act_host's refusals (the satrl_* slot)
 #include "scripted_device.h"   // satrl_scripted_act_host (include/satrl_ppo.h)
 
 using namespace satenv;
@@ -242,7 +243,8 @@ int satenv_cpu_check(satenv_cpu_env* h, int32_t* status) {
 // A scripted opponent's law on host pointers (include/satrl_ppo.h): the
 // kernels' own source, one loop iteration per env row, no device call.
 int satrl_scripted_act_host(int64_t N, const float* obs, const satrl_scripted_law* law, float* act) {
-  if (N <= 0 || !obs || !law || !act) return -1;
+  if (N <= 0) return satrl_err::fail(-1, __func__, "N " + std::to_string(N) + " <= 0");
+  if (int rc = satrl_err::null_arg(__func__, SATRL_PTRS(obs, law, act))) return rc;
   for (int64_t i = 0; i < N; ++i) satrl_scripted::law_row(law, obs + i * 18, act + i * 3);
   return 0;
 }

@@ -1,9 +1,14 @@
 """ctypes binding of the product's C-ABI library ``libsatrl.so``.
 
-The library exports exactly the functions declared in ``include/satenv.h``
-and ``include/satrl_rollout.h`` (plain pointers, sizes and a ``void*``
-hipStream_t).  It is built in-tree by ``csrc/Makefile`` for gfx950.  There is
-no fallback: if the library is missing or cannot be loaded, every op raises.
+The library exports exactly the functions declared in ``include/satenv.h``,
+``satenv_cpu.h``, ``satrl_rollout.h``, ``satrl_ppo.h`` and ``satrl_peer.h``
+(plain pointers, sizes and a ``void*`` hipStream_t); ``_SIGS`` restates their
+signatures.  A refused call returns a negative code and leaves
+``"<entry point>: <reason>"`` in its ABI's error slot: one for ``satenv_*``,
+one for ``satenv_cpu_*`` and one shared by every ``satrl_*`` entry point
+(``check`` raises with it).  It is built in-tree by ``csrc/Makefile`` for
+gfx950.  There is no fallback: if the library is missing or cannot be loaded,
+every op raises.
 
 torch is imported first so that the process has a single HIP runtime
 (torch's bundled ``libamdhip64.so.7``; the library's NEEDED entry resolves to
@@ -237,13 +242,9 @@ def lib():
 def check(rc: int, what: str):
     if rc != 0:
         L = lib()
-        msg = (L.satenv_cpu_last_error() if what.startswith("satenv_cpu") else
-               L.satenv_last_error() if what.startswith("satenv") else
-               L.satrl_ppo_last_error() if what.startswith(("satrl_ppo", "satrl_peer", "satrl_policy_act_pool",
-                                                                   "satrl_opponent_assign", "satrl_scripted_act",
-                                                                   "satrl_policy_act_scripted",
-                                                                   "satrl_policy_eval_scripted")) else
-               L.satrl_last_error()).decode()
+        msg = (L.satenv_cpu_last_error() if what.startswith("satenv_cpu_") else
+               L.satenv_last_error() if what.startswith("satenv_") else
+               L.satrl_last_error()).decode()      # every satrl_* entry point: one slot
         raise NativeError(f"{what} failed ({rc}): {msg}")
 
 

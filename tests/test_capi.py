@@ -52,16 +52,113 @@ def test_host_helpers_without_gpu():
     assert np.array_equal(E.stm(100.0), O.stm(100.0))
 
 
+def _slot(lib):
+    """The satrl_* error slot; both accessors return it."""
+    msg = lib.satrl_last_error()
+    assert lib.satrl_ppo_last_error() == msg
+    return msg
+
+
+def _poison(lib, name):
+    """Leave another entry point's refusal in the slot, so that a refusal of
+    `name` that writes nothing cannot pass for one that names itself."""
+    other = "satrl_moments" if name == "satrl_gae" else "satrl_gae"
+    args = (0, None, None, None) if other == "satrl_moments" else (0, 0, None, None, None, 0.0, 0.0, None, None, None)
+    assert getattr(lib, other)(*args) == -1
+    assert _slot(lib).startswith(other.encode() + b": ")
+
+
+def _refused(lib, name, *args, code=-1, words=()):
+    """`name(*args)` returns `code` and leaves "<name>: <reason>" with every one of `words` in the reason."""
+    _poison(lib, name)
+    assert getattr(lib, name)(*args) == code, (name, args)
+    msg = _slot(lib)
+    assert msg.startswith(name.encode() + b": "), msg
+    for w in words:
+        assert w in msg[len(name) + 2:], (w, msg)
+    return True
+
+
+def test_every_satrl_refusal_names_its_entry_point():
+    """Every satrl_* symbol of _lib._SIGS (one added later included), called
+    with all-zero / NULL arguments, returns a negative code and leaves
+    "<symbol>: <reason>" in the shared slot, which held another entry point's
+    text before the call.  Nothing on these paths reaches a device."""
+    import satrl._lib as L
+    lib = L.lib()
+
+    def zero(t):
+        return None if t is C.c_void_p or issubclass(t, C._Pointer) else t(0).value
+
+    # the whole exception list: each has its own case below
+    special = {"satrl_last_error", "satrl_ppo_last_error", "satrl_span_probe", "satrl_span_probe_launches",
+               "satrl_ppo_rowpass_sync", "satrl_ppo_rowpass_fault_inject"}
+    names = [n for n in L.exported_symbols() if n.startswith("satrl_")]
+    assert special <= set(names) and len(names) > 50
+    for name in names:
+        if name in special:
+            continue
+        argt, _ = L._SIGS[name]
+        _poison(lib, name)
+        rc = getattr(lib, name)(*[zero(t) for t in argt])
+        assert rc < 0, (name, rc)
+        assert _slot(lib).startswith(name.encode() + b": "), (name, _slot(lib))
+    # the two accessors return the one slot (_slot compares them)
+    _poison(lib, "satrl_last_error")
+    # zeros are valid here: no probe buffer, and no launch logged in a process without one
+    assert lib.satrl_span_probe(None, 0, None) == 0 and lib.satrl_span_probe_launches() == 0
+    assert _refused(lib, "satrl_span_probe", None, 8, None, words=(b"bytes",))
+    # modes 0 and 1 flip a process-wide switch, so only the refused mode is called
+    assert _refused(lib, "satrl_ppo_rowpass_sync", 2, words=(b"mode",))
+    assert _refused(lib, "satrl_ppo_rowpass_fault_inject", -1, 0, None, words=(b"group",))
+
+
+def test_check_reports_the_failing_entry_point():
+    """_lib.check raises with the refused call's own text, whichever source
+    file the entry point lives in and whatever failed before it."""
+    import satrl._lib as L
+    lib = L.lib()
+    fake = C.c_void_p(16)
+    H, mb = 256, 4096
+    kx = lib.satrl_ppo_kx_elems(H, mb)
+    # two refusals of other entry points first: 16 splits into slabs for 8, and an empty scratch
+    assert lib.satrl_ppo_dw2_kx(H, mb, -1, 16, fake, fake, kx, fake, 2 * 8 * H * H, None) == -1
+    assert _slot(lib).startswith(b"satrl_ppo_dw2_kx: p2 holds")
+    assert lib.satrl_moments_ordered(1000, fake, fake, fake, 0, None) == -1
+    assert _slot(lib).startswith(b"satrl_moments_ordered: scratch holds 0 doubles")
+    rc = lib.satrl_policy_act(256, 8, fake, fake, fake, 1.6, 0, 0, 0, None, fake, fake, None, None, None)
+    with pytest.raises(L.NativeError, match=r"^satrl_policy_act failed \(-1\): satrl_policy_act: act1"):
+        L.check(rc, "satrl_policy_act")
+    assert lib.satrl_ppo_dw2_kx(H, mb, -1, 16, fake, fake, kx, fake, 2 * 8 * H * H, None) == -1
+    rc = lib.satrl_ppo_rowpass(100, 64, -1, fake, None, fake, fake, 0.1, 0.01, 1.6, fake, fake, fake, fake, None)
+    with pytest.raises(L.NativeError, match=r"^satrl_ppo_rowpass failed \(-1\): satrl_ppo_rowpass: H 100"):
+        L.check(rc, "satrl_ppo_rowpass")
+    # an entry point of the host build's source file writes the same slot
+    rc = lib.satrl_scripted_act_host(2, fake, None, fake)
+    with pytest.raises(L.NativeError, match=r"^satrl_scripted_act_host failed \(-1\): satrl_scripted_act_host: law"):
+        L.check(rc, "satrl_scripted_act_host")
+    # the env ABIs keep their own slots
+    with pytest.raises(L.NativeError, match=r"satenv_cpu_num_envs failed \(-1\): satenv_cpu_num_envs"):
+        L.check(lib.satenv_cpu_num_envs(None, None), "satenv_cpu_num_envs")
+    with pytest.raises(L.NativeError, match=r"satenv_create failed \(-1\): satenv_create"):
+        L.check(lib.satenv_create(None, 4, None, 0), "satenv_create")
+
+
 def test_entry_points_reject_bad_arguments_before_any_device_call():
     """Error behaviour of the boundary (include/*.h: 0 ok, negative codes):
     shapes, widths and null pointers are checked on the host before any HIP
     call, so these run without a GPU.  A non-null dummy pointer is never
-    dereferenced on these paths."""
+    dereferenced on these paths.  Every learner-side refusal names its entry
+    point and says which check failed."""
     import ctypes as C
     import satrl._lib as L
     from satrl import env as E
     lib = L.lib()
     fake = C.c_void_p(16)                       # never touched: every call below fails its host checks
+
+    def no(name, *args, words=()):
+        return _refused(lib, name, *args, words=words)
+
     # satenv_create: null out / null params / num_envs <= 0 / bad propagator -> SATENV_ERR_ARG (-1)
     p = E.default_params()
     h = C.c_void_p()
@@ -77,57 +174,69 @@ def test_entry_points_reject_bad_arguments_before_any_device_call():
     assert lib.satenv_set_step_kernel(fake, 2, 48) == -1                       # 16 / 32 / 64 envs per workgroup
     # learner side: unsupported hidden width, empty minibatch, net out of range, null buffers
     off = (C.c_int64 * 16)()
-    assert lib.satrl_ppo_layout(100, off) == -1 and lib.satrl_ppo_layout(256, off) == 0
-    assert lib.satrl_ppo_sizes(256, 0, None, None) == -1
+    assert no("satrl_ppo_layout", 100, off, words=(b"H 100",)) and lib.satrl_ppo_layout(256, off) == 0
+    assert no("satrl_ppo_sizes", 256, 0, None, None, words=(b"mb 0",))
     args = [fake, None, fake, fake, 0.1, 0.01, 1.6, fake, fake, fake, fake, None]
-    assert lib.satrl_ppo_rowpass(100, 64, -1, *args) == -1                     # H not 64/128/256
-    assert lib.satrl_ppo_rowpass(256, 0, -1, *args) == -1                      # empty minibatch
-    assert lib.satrl_ppo_rowpass(256, 64, 2, *args) == -1                      # net not -1/0/1
-    assert lib.satrl_ppo_rowpass(256, 64, -1, None, *args[1:]) == -1           # null rows
+    assert no("satrl_ppo_rowpass", 100, 64, -1, *args, words=(b"H 100", b"64/128/256"))   # H not 64/128/256
+    assert no("satrl_ppo_rowpass", 256, 0, -1, *args, words=(b"mb 0", b"empty"))          # empty minibatch
+    assert no("satrl_ppo_rowpass", 256, 64, 2, *args, words=(b"net 2", b"-1 .. 1"))       # net not -1/0/1
+    assert no("satrl_ppo_rowpass", 256, 64, -1, None, *args[1:], words=(b"src is NULL",))  # null rows
     big = 1 << 40                                # a p2 / plane capacity no call exceeds
-    assert lib.satrl_ppo_dw2(256, 4096, -1, 0, fake, fake, fake, big, None) == -1   # S < 1
-    assert lib.satrl_ppo_dw2(256, 64, -1, 64, fake, fake, fake, big, None) == -1    # an empty split
-    assert lib.satrl_ppo_reduce(256, 64, -1, 1, 4, fake, big, fake, fake, fake, fake, fake, None) == -1   # mode
-    assert lib.satrl_ppo_reduce(256, 64, -1, 1, 2, fake, big, fake, fake, fake, None, None, None) == -1   # no nsq
-    assert lib.satrl_gae(0, 4, fake, fake, fake, 0.99, 0.95, fake, fake, None) == -1
-    assert lib.satrl_gae(4, 4, fake, None, fake, 0.99, 0.95, fake, fake, None) == -1
-    assert lib.satrl_policy_act(256, 8, fake, fake, fake, 1.6, 0, 0, 0, None, fake, fake, None, None,
-                                None) == -1                                   # second agent without outputs
-    assert lib.satrl_ppo_tanh(0, fake, fake, None) == -1
+    assert no("satrl_ppo_dw2", 256, 4096, -1, 0, fake, fake, fake, big, None, words=(b"S 0 < 1",))      # S < 1
+    assert no("satrl_ppo_dw2", 256, 64, -1, 64, fake, fake, fake, big, None,
+              words=(b"empty split", b"satrl_ppo_dw2_splits"))                                          # an empty split
+    assert no("satrl_ppo_reduce", 256, 64, -1, 1, 4, fake, big, fake, fake, fake, fake, fake, None,
+              words=(b"mode",))                                                                         # mode
+    assert no("satrl_ppo_reduce", 256, 64, -1, 1, 2, fake, big, fake, fake, fake, None, None, None,
+              words=(b"nsq is NULL",))                                                                  # no nsq
+    assert no("satrl_gae", 0, 4, fake, fake, fake, 0.99, 0.95, fake, fake, None, words=(b"T must",))
+    assert no("satrl_gae", 4, 4, fake, None, fake, 0.99, 0.95, fake, fake, None, words=(b"done is NULL",))
+    assert no("satrl_policy_act", 256, 8, fake, fake, fake, 1.6, 0, 0, 0, None, fake, fake, None, None, None,
+              words=(b"act1 is NULL",))                                       # second agent without outputs
+    assert no("satrl_ppo_tanh", 0, fake, fake, None, words=(b"n 0",))
     # the fc2 operand image and the k-packed dW2 path (H = 256, mb above the 16-row threshold)
     assert lib.satrl_ppo_w2x_floats(256) == 2 * 256 * 256                    # the f32 W2^T at every width
     assert lib.satrl_ppo_w2x_floats(64) == 2 * 64 * 64
-    assert lib.satrl_ppo_w2x_floats(100) == -1
-    assert lib.satrl_ppo_w2x_sync(100, -1, fake, fake, None) == -1 and lib.satrl_ppo_w2x_sync(256, -1, None, fake, None) == -1
+    assert no("satrl_ppo_w2x_floats", 100, words=(b"H 100",))
+    assert no("satrl_ppo_w2x_sync", 100, -1, fake, fake, None, words=(b"H 100",))
+    assert no("satrl_ppo_w2x_sync", 256, -1, None, fake, None, words=(b"P is NULL",))
     assert lib.satrl_ppo_kx_elems(256, 4096) == 2 * 3 * 4096 * 256 and lib.satrl_ppo_kx_elems(256, 1500) == 6 * 1504 * 256
-    assert lib.satrl_ppo_kx_elems(64, 4096) == -1
+    assert no("satrl_ppo_kx_elems", 64, 4096, words=(b"H 64 is not 256",))
     kx_args = args[:9] + [big] + args[9:]        # (H1x, dZ2x, kx_elems, ptail, pw1, stream)
-    assert lib.satrl_ppo_rowpass_kx(256, 512, -1, None, *kx_args[1:]) == -1     # null rows (16-row kernel's minibatch)
-    assert lib.satrl_ppo_rowpass_kx(64, 4096, -1, *kx_args) == -1               # H 256 only
+    assert no("satrl_ppo_rowpass_kx", 256, 512, -1, None, *kx_args[1:],
+              words=(b"src is NULL",))                                        # null rows (16-row kernel's minibatch)
+    assert no("satrl_ppo_rowpass_kx", 64, 4096, -1, *kx_args, words=(b"H 64 is not 256",))   # H 256 only
     assert lib.satrl_ppo_dw2_kx_splits(256, 4096, -1) == 8 and lib.satrl_ppo_dw2_kx_splits(256, 4096, 0) == 16
-    assert lib.satrl_ppo_dw2_kx(256, 4096, -1, 0, fake, fake, big, fake, big, None) == -1     # S < 1
-    assert lib.satrl_ppo_dw2_kx(256, 64, -1, 3, fake, fake, big, fake, big, None) == -1       # an empty split (2 chunks)
-    assert lib.satrl_ppo_dw2_kx(256, 4096, -1, 8, None, fake, big, fake, big, None) == -1     # null H1x
+    assert no("satrl_ppo_dw2_kx", 256, 4096, -1, 0, fake, fake, big, fake, big, None, words=(b"S 0 < 1",))   # S < 1
+    assert no("satrl_ppo_dw2_kx", 256, 64, -1, 3, fake, fake, big, fake, big, None,
+              words=(b"empty split", b"satrl_ppo_dw2_kx_splits"))             # an empty split (2 chunks)
+    assert no("satrl_ppo_dw2_kx", 256, 4096, -1, 8, None, fake, big, fake, big, None,
+              words=(b"H1x is NULL",))                                        # null H1x
     w1a = [fake, fake, big, fake, big]                     # (H1x, dZ2x, kx_elems, p2, p2_floats)
-    assert lib.satrl_ppo_dw2_kx_w1(256, 4096, -1, 8, *w1a, 2, fake, fake, fake, fake, None) == -1   # mode 1 or 3
-    assert lib.satrl_ppo_dw2_kx_w1(256, 4096, -1, 8, *w1a, 3, None, fake, fake, fake, None) == -1   # null p1
-    assert lib.satrl_ppo_dw2_kx_w1(256, 4096, -1, 8, *w1a, 3, fake, fake, fake, None, None) == -1   # mode 3: nsq
-    assert lib.satrl_ppo_dw2_kx_w1(64, 4096, -1, 8, *w1a, 1, fake, fake, fake, None, None) == -1    # H 256 only
-    assert lib.satrl_ppo_reduce(256, 4096, -1, 8, 6, fake, big, None, None, fake, fake, fake, None) == -1  # 4 needs 1
-    assert lib.satrl_ppo_rowpass_error(None, 1.0, None) == -1                 # the column-split kernel's error word
-    assert lib.satrl_ppo_rowpass_error(C.byref(C.c_int()), 0.0, None) == -1  # no deadline
-    assert lib.satrl_ppo_rowpass_fault_inject(-1, 0, None) == -1 and lib.satrl_ppo_rowpass_fault_inject(1 << 20, 0, None) == -1
+    w1 = "satrl_ppo_dw2_kx_w1"
+    assert no(w1, 256, 4096, -1, 8, *w1a, 2, fake, fake, fake, fake, None, words=(b"mode 2", b"1 or 3"))  # mode 1 or 3
+    assert no(w1, 256, 4096, -1, 8, *w1a, 3, None, fake, fake, fake, None, words=(b"p1 is NULL",))       # null p1
+    assert no(w1, 256, 4096, -1, 8, *w1a, 3, fake, fake, fake, None, None, words=(b"nsq", b"mode 3"))    # mode 3: nsq
+    assert no(w1, 64, 4096, -1, 8, *w1a, 1, fake, fake, fake, None, None, words=(b"H 64 is not 256",))   # H 256 only
+    assert no("satrl_ppo_reduce", 256, 4096, -1, 8, 6, fake, big, None, None, fake, fake, fake, None,
+              words=(b"bit 4", b"without 1"))                                 # 4 needs 1
+    assert no("satrl_ppo_rowpass_error", None, 1.0, None, words=(b"err is NULL",))   # the column-split kernel's error word
+    assert no("satrl_ppo_rowpass_error", C.byref(C.c_int()), 0.0, None, words=(b"deadline",))   # no deadline
+    assert no("satrl_ppo_rowpass_fault_inject", -1, 0, None, words=(b"group -1",))
+    assert no("satrl_ppo_rowpass_fault_inject", 1 << 20, 0, None, words=(b"group 1048576",))
     # the peer all-reduce: grid, deadline, buffers
     bufs = (C.c_void_p * 2)(16, 16)
     pa = [C.cast(bufs, C.c_void_p), fake, fake, fake]
-    assert lib.satrl_ppo_allreduce_peer(256, 512, 2, 0, *pa, 0, 10.0, None) == -1            # no blocks
-    assert lib.satrl_ppo_allreduce_peer(256, 512, 2, 0, *pa, 2048, 10.0, None) == -1         # > kPeerMaxBlocks
-    assert lib.satrl_ppo_allreduce_peer(256, 512, 2, 0, *pa, 256, 0.0, None) == -1           # no deadline
-    assert lib.satrl_ppo_allreduce_peer(256, 512, 2, 2, *pa, 256, 10.0, None) == -1          # rank >= world
-    assert lib.satrl_ppo_allreduce_peer(256, 512, 9, 0, *pa, 256, 10.0, None) == -1          # world > 8
-    assert lib.satrl_peer_blocks(100, C.byref(C.c_int())) == -1 and lib.satrl_peer_blocks(256, None) == -1
-    assert lib.satrl_peer_error(None, C.byref(C.c_uint64()), None) == -1
-    assert lib.satrl_peer_reset(fake, 8, None) == -1                                         # smaller than the header
+    ar = "satrl_ppo_allreduce_peer"
+    assert no(ar, 256, 512, 2, 0, *pa, 0, 10.0, None, words=(b"blocks 0",))                  # no blocks
+    assert no(ar, 256, 512, 2, 0, *pa, 2048, 10.0, None, words=(b"blocks 2048", b"1024"))    # > kPeerMaxBlocks
+    assert no(ar, 256, 512, 2, 0, *pa, 256, 0.0, None, words=(b"deadline",))                 # no deadline
+    assert no(ar, 256, 512, 2, 2, *pa, 256, 10.0, None, words=(b"rank 2", b"0 .. 1"))        # rank >= world
+    assert no(ar, 256, 512, 9, 0, *pa, 256, 10.0, None, words=(b"world 9", b"8"))            # world > 8
+    assert no("satrl_peer_blocks", 100, C.byref(C.c_int()), words=(b"H 100",))
+    assert no("satrl_peer_blocks", 256, None, words=(b"blocks is NULL",))
+    assert no("satrl_peer_error", None, C.byref(C.c_uint64()), None, words=(b"buf is NULL",))
+    assert no("satrl_peer_reset", fake, 8, None, words=(b"header",))                         # smaller than the header
 
 
 def test_capi_refuses_calls_past_the_callers_buffers():
@@ -145,21 +254,25 @@ def test_capi_refuses_calls_past_the_callers_buffers():
     kx = lib.satrl_ppo_kx_elems(H, mb)
     p2_8 = 2 * 8 * H * H                                         # slabs sized for 8 splits
     # an oversize split count (the round-5 case: 16 splits into slabs for 8)
-    assert lib.satrl_ppo_dw2_kx(H, mb, -1, 16, fake, fake, kx, fake, p2_8, None) == -1
+    def no(name, *args, words):
+        return _refused(lib, name, *args, words=words)
+
+    assert no("satrl_ppo_dw2_kx", H, mb, -1, 16, fake, fake, kx, fake, p2_8, None, words=(b"p2 holds", b"16 splits"))
     assert b"p2 holds" in lib.satrl_ppo_last_error()
-    assert lib.satrl_ppo_reduce(H, mb, -1, 16, 3, fake, p2_8, fake, fake, fake, fake, fake, None) == -1
+    assert no("satrl_ppo_reduce", H, mb, -1, 16, 3, fake, p2_8, fake, fake, fake, fake, fake, None,
+              words=(b"p2 holds", b"16 splits"))
     assert b"p2 holds" in lib.satrl_ppo_last_error()
-    assert lib.satrl_ppo_dw2(H, mb, -1, 16, fake, fake, fake, p2_8, None) == -1
+    assert no("satrl_ppo_dw2", H, mb, -1, 16, fake, fake, fake, p2_8, None, words=(b"p2 holds", b"16 splits"))
     # one net: the actor passes half, the critic (second half) the whole buffer
-    assert lib.satrl_ppo_dw2_kx(H, mb, 1, S, fake, fake, kx, fake, p2_8 // 2, None) == -1
+    assert no("satrl_ppo_dw2_kx", H, mb, 1, S, fake, fake, kx, fake, p2_8 // 2, None, words=(b"p2 holds",))
     # undersized planes, for the rowpass that writes them and the dW2 that reads them
-    assert lib.satrl_ppo_rowpass_kx(H, mb, -1, fake, None, fake, fake, 0.1, 0.01, 1.6, fake, fake, kx - 1, fake,
-                                    fake, None) == -1
+    assert no("satrl_ppo_rowpass_kx", H, mb, -1, fake, None, fake, fake, 0.1, 0.01, 1.6, fake, fake, kx - 1, fake,
+              fake, None, words=(b"planes hold",))
     assert b"planes hold" in lib.satrl_ppo_last_error()
-    assert lib.satrl_ppo_dw2_kx(H, mb, -1, S, fake, fake, kx - 1, fake, p2_8, None) == -1
+    assert no("satrl_ppo_dw2_kx", H, mb, -1, S, fake, fake, kx - 1, fake, p2_8, None, words=(b"planes hold",))
     # H 64: one slab per 32-row block (128 at mb 4096) written by the fused rowpass
-    assert lib.satrl_ppo_rowpass_dw2(64, mb, -1, fake, None, fake, fake, 0.1, 0.01, 1.6, fake, 2 * 127 * 64 * 64,
-                                     fake, fake, None) == -1
+    assert no("satrl_ppo_rowpass_dw2", 64, mb, -1, fake, None, fake, fake, 0.1, 0.01, 1.6, fake, 2 * 127 * 64 * 64,
+              fake, fake, None, words=(b"p2 holds", b"128 splits"))
     assert b"p2 holds" in lib.satrl_ppo_last_error()
 
 
