@@ -346,6 +346,54 @@ int satrl_policy_eval_scripted(int H, int64_t N, const float* obs, const float* 
                                int agent /* 0 | 1 */, float max_action, int det /* 0 | 1 */, uint64_t seed,
                                int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act,
                                const satrl_scripted_law* law /* device */, float* act_scripted, void* stream);
+/* League play: satrl_policy_act_pool with a table of J laws behind the K
+ * stored sets.  Per 32-row block b of agent pool_agent, m = member[b]:
+ *   0 <= m < K       the stored set pool + m * pool_stride, as the pooled call
+ *   K <= m < K + J   law j = m - K: the workgroup branches uniformly round the
+ *                    whole MLP (no parameter, no LDS, no barrier); rows r of
+ *                    the block get act = the law laws[j] over obs_law's row
+ *                    (bit for bit satrl_scripted_act) and logp = +0.0f
+ *   anything else    (-1, K + J, INT_MIN, ...) the live P0 / P1
+ * No value of m makes the kernel read outside pool or laws.  A stored or live
+ * block's rows and all of the other agent's rows are bit for bit those of
+ * satrl_policy_act with that block's parameter set; the Philox keys, the
+ * counter, env_offset, step and step_base are satrl_policy_act_pool's.
+ * obs_law f32 [N][18] is the raw observation and may equal obs; laws is a
+ * DEVICE array satrl_scripted_law[J].  member, pool and laws are read at every
+ * launch: a captured graph follows in-place changes of all three with no
+ * recapture.
+ * -1 before any device call (satrl_ppo_last_error says which): every refusal
+ * of satrl_policy_act_pool; a NULL obs_law or laws; J outside
+ * 1 .. SATRL_LEAGUE_MAX_LAWS; laws not 8-byte aligned.
+ * Span probe: as the pooled kernel, no probed instantiation; nothing is
+ * logged for these launches.                                               */
+#define SATRL_LEAGUE_MAX_LAWS 8
+int satrl_policy_act_league(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
+                            uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act0,
+                            float* logp0, float* act1, float* logp1, int pool_agent /* 0 | 1 */,
+                            const float* pool /* [K][pool_stride] */, int64_t pool_stride, int K,
+                            const int32_t* member /* [ceil(N/32)], device */, const float* obs_law,
+                            const satrl_scripted_law* laws /* [J], device */, int J, void* stream);
+/* Which league member each 32-env block plays this iteration: the rule of
+ * satrl_opponent_assign with laws and weighted stored opponents.  Host only.
+ * For global block g = first_block + i, with w and u as satrl_opponent_assign
+ * forms them (the same Philox word), in this order:
+ *   1. (filled == 0 && n_laws == 0) || u < latest_prob:          m = -1
+ *   2. n_laws > 0 && (filled == 0 || u < latest_prob + law_prob): m = K + ((w[2] * n_laws) >> 32)
+ *   3. weights == NULL:                                          m = (w[1] * filled) >> 32
+ *   4. else, S = weights[0] + .. + weights[filled - 1] in f64, ascending k,
+ *      v = (w[1] + 0.5) * 2^-32 * S: m = the first k whose running sum c_k has
+ *      v < c_k, and the last k with weights[k] > 0 when none has.
+ * With n_laws == 0 and weights == NULL the output is satrl_opponent_assign's.
+ * It depends on (seed, iteration, g, K, filled, n_laws, the probabilities,
+ * weights) alone, never on the sharding.  weights is read when filled > 0.
+ * -1: a NULL member_out; n_blocks <= 0; first_block < 0; K < 0; filled outside
+ * 0 .. K; n_laws outside 0 .. SATRL_LEAGUE_MAX_LAWS; latest_prob or law_prob
+ * outside [0, 1] or NaN; latest_prob + law_prob > 1; a weight that is
+ * negative or not finite; a weight sum that is not positive.               */
+int satrl_league_assign(uint64_t seed, uint64_t iteration, int64_t first_block, int64_t n_blocks, int K, int filled,
+                        int n_laws, double latest_prob, double law_prob,
+                        const double* weights /* NULL | host [filled] */, int32_t* member_out /* host */);
 /* critic value v f32 [N] of the flat parameters P (net 1) <- self.critic(s),
  * ppo_continuous.py:200-201                                               */
 int satrl_policy_value(int H, int64_t N, const float* obs, const float* P, float* v_out, void* stream);

@@ -102,6 +102,20 @@ int satrl_episode_record(int64_t N, const double* reward, const uint8_t* done, c
                          const float* ea, double capture_reward, double* rec_f64, int32_t* rec_i32, int32_t* alive,
                          void* stream);
 
+/* League tally: a rollout's finished episodes and captures per 32-env block,
+ * from the rollout table itself.  rew f32 [T][N], done u8 [T][N]; for block
+ * b (envs 32 b .. 32 b + 31, the ragged last block its valid envs only):
+ *   tally[b][0] += steps (t, env) with done != 0
+ *   tally[b][1] += those of them with rew == capture_reward
+ * tally i64 [ceil(N/32)][2] on the device, added to.  capture_reward is the
+ * f32 literal the env writes at a capture (it differs from the timeout's).
+ * Integer sums: exact, independent of order and sharding; a block belongs to
+ * one half-wave, so there are no atomics.  -1 before any device call: T or N
+ * not positive, T above INT32_MAX (a lane counts in 32 bits), a NULL rew,
+ * done or tally.                                                            */
+int satrl_league_tally(int64_t T, int64_t N, const float* rew, const uint8_t* done, float capture_reward,
+                       int64_t* tally, void* stream);
+
 /* "<entry point>: <reason>" of this thread's last refused satrl_* call (the
  * slot satrl_ppo_last_error of satrl_ppo.h returns too).                  */
 const char* satrl_last_error(void);

@@ -1823,8 +1823,15 @@ constexpr int kPolNW = 8;      // waves per policy workgroup at H = 256 (16: 61.
 // observation float4, which does not depend on it, goes out under it rather
 // than behind the W1 rows that do.  With POOL false every pool argument is
 // dead and the code is policy_kernel's as it was (the
-// resource tables).
-template <int H, int NW, int MODE, bool SPAN, bool POOL>
+// resource tables).  LEAGUE (the pooled form with a law table, DESIGN.md
+// 3.2.3): K <= m < K + J names law m - K, and that workgroup branches
+// uniformly round the whole MLP -- no parameter, no LDS access, no barrier --
+// its lanes r < nvalid evaluating the law on obs_law and writing +0.0f
+// log-probs.  j is formed from the first lane's m (readfirstlane): law_row
+// reads the law through the constant address space, which needs a provably
+// wave-uniform address.  With LEAGUE false obs_law, laws and J are dead and the
+// instantiations are as they were (3.2.3, the resource tables).
+template <int H, int NW, int MODE, bool SPAN, bool POOL, bool LEAGUE = false>
 __device__ __forceinline__ void policy_body(int64_t N, const float* __restrict__ obs, const float* __restrict__ P0,
                                             const float* __restrict__ P1, int nagents, float max_action, uint32_t k00,
                                             uint32_t k01, uint32_t k10, uint32_t k11, int64_t env_offset,
@@ -1834,8 +1841,10 @@ __device__ __forceinline__ void policy_body(int64_t N, const float* __restrict__
                                             float* __restrict__ value, int det_mask,
                                             unsigned long long* __restrict__ span, const float* __restrict__ pool,
                                             const int32_t* __restrict__ member, int64_t pool_stride, int K,
-                                            int pool_agent) {
+                                            int pool_agent, const float* __restrict__ obs_law = nullptr,
+                                            const satrl_scripted_law* __restrict__ laws = nullptr, int J = 0) {
   static_assert(!POOL || (MODE == 0 && !SPAN), "the pooled form is the product MODE 0 kernel");
+  static_assert(!LEAGUE || POOL, "the league form is the pooled one with a law table");
   const unsigned long long span_t0 = SPAN ? satrl_span::now() : 0ull;
   constexpr int R = kPolRows, RT = R / 16, CT = H / 16 / NW;
   // Two or more workgroups share a CU, and one finishing its output layer
@@ -1859,6 +1868,22 @@ __device__ __forceinline__ void policy_body(int64_t N, const float* __restrict__
     if (nvalid == R && (reinterpret_cast<uintptr_t>(ob) & 15) == 0 && (int)threadIdx.x < R * 18 / 4)
       pre = reinterpret_cast<const float4*>(ob)[threadIdx.x];
     if ((unsigned)m < (unsigned)K) P = pool + (int64_t)m * pool_stride;   // (m stays -1 for the other agent; K > 0)
+  }
+  if constexpr (LEAGUE) {
+    // m - K in unsigned arithmetic: every m outside [K, K + J) wraps past J (J <= 8), the other agent's -1 too
+    const unsigned j = (unsigned)__builtin_amdgcn_readfirstlane(m) - (unsigned)K;
+    if (j < (unsigned)J) {                                       // (uniform: the whole workgroup leaves here)
+      const int r = threadIdx.x;
+      if (r < nvalid) {
+        const int64_t i = r0 + r;
+        satrl_scripted::law_row(laws + j, obs_law + i * 18, (agent == 0 ? act0 : act1) + i * 3);
+        float* lp = (agent == 0 ? logp0 : logp1) + i * 3;
+        lp[0] = 0.0f;
+        lp[1] = 0.0f;
+        lp[2] = 0.0f;
+      }
+      return;
+    }
   }
   auto gather = [&](int t0, int nt) {
     const float* ob = obs + r0 * 18;
@@ -1965,6 +1990,31 @@ __global__ void __launch_bounds__(NW * 64) policy_pool_kernel(int64_t N, const f
   policy_body<H, NW, 0, false, true>(N, obs, P0, P1, 2, max_action, k00, k01, k10, k11, env_offset, step, step_base,
                                      act0, logp0, act1, logp1, nullptr, 0, nullptr, pool, member, pool_stride, K,
                                      pool_agent);
+}
+
+// The league MODE 0 kernel (satrl_policy_act_league): the pooled kernel with a
+// table of J laws behind the K stored sets.  Its first 14 argument dwords are
+// what either branch's first loads and the branch itself need: N, obs, pool,
+// member, pool_stride, K, pool_agent, J and max_action (P0, P1, obs_law and
+// laws follow by s_load under the member load).  No SPAN instantiation, as
+// for the pooled kernel.
+template <int H, int NW>
+__global__ void __launch_bounds__(NW * 64) policy_league_kernel(int64_t N, const float* __restrict__ obs,
+                                                            const float* __restrict__ pool,
+                                                            const int32_t* __restrict__ member, int64_t pool_stride,
+                                                            int K, int pool_agent, int J, float max_action,
+                                                            const float* __restrict__ P0,
+                                                            const float* __restrict__ P1,
+                                                            const float* __restrict__ obs_law,
+                                                            const satrl_scripted_law* __restrict__ laws, uint32_t k00,
+                                                            uint32_t k01, uint32_t k10, uint32_t k11,
+                                                            int64_t env_offset, uint64_t step,
+                                                            const uint64_t* __restrict__ step_base,
+                                                            float* __restrict__ act0, float* __restrict__ logp0,
+                                                            float* __restrict__ act1, float* __restrict__ logp1) {
+  policy_body<H, NW, 0, false, true, true>(N, obs, P0, P1, 2, max_action, k00, k01, k10, k11, env_offset, step,
+                                           step_base, act0, logp0, act1, logp1, nullptr, 0, nullptr, pool, member,
+                                           pool_stride, K, pool_agent, obs_law, laws, J);
 }
 
 // ---------------------------------------------------------------------------
@@ -3815,6 +3865,90 @@ int satrl_opponent_assign(uint64_t seed, uint64_t iteration, int64_t first_block
     philox4x32_10(w, k0, k1);
     const double u = ((double)w[0] + 0.5) * (1.0 / 4294967296.0);
     member_out[i] = (filled == 0 || u < latest_prob) ? -1 : (int32_t)(((uint64_t)w[1] * (uint64_t)filled) >> 32);
+  }
+  return 0;
+}
+
+int satrl_policy_act_league(int H, int64_t N, const float* obs, const float* P0, const float* P1, float max_action,
+                            uint64_t seed, int64_t env_offset, uint64_t step, const uint64_t* step_base, float* act0,
+                            float* logp0, float* act1, float* logp1, int pool_agent, const float* pool,
+                            int64_t pool_stride, int K, const int32_t* member, const float* obs_law,
+                            const satrl_scripted_law* laws, int J, void* stream) {
+  if (int rc = refuse(__func__, H, kAnyH, N, "N", 0, SATRL_PTRS(obs, P0, act0, logp0))) return rc;
+  if (!P1 || !act1 || !logp1) return fail(-1, __func__, "both agents are required: a NULL P1, act1 or logp1");
+  if (pool_agent != 0 && pool_agent != 1) return fail(-1, __func__, "pool_agent is 0 or 1");
+  if (int rc = null_arg(__func__, SATRL_PTRS(pool, member, obs_law, laws))) return rc;
+  if (K <= 0) return fail(-1, __func__, "K <= 0");
+  if (pool_stride < layout(H).total || pool_stride % 4 != 0)
+    return fail(-1, __func__, "pool_stride below the layout total or not a multiple of 4");
+  if (reinterpret_cast<uintptr_t>(pool) & 15) return fail(-1, __func__, "pool is not 16-byte aligned");
+  if (J < 1 || J > SATRL_LEAGUE_MAX_LAWS)
+    return fail(-1, __func__, "J " + to_string(J) + " is outside 1 .. " + to_string(SATRL_LEAGUE_MAX_LAWS));
+  if (reinterpret_cast<uintptr_t>(laws) & 7) return fail(-1, __func__, "laws is not 8-byte aligned");
+  const PolicyKeys k(seed);
+  const char* who = __func__;
+  // (no SPAN form, as satrl_policy_act_pool)
+  return with_width<kPolNW>(H, [&](auto w) {
+    using W = decltype(w);
+    return launch(who, policy_league_kernel<W::H, W::NW>, 2 * ((N + kPolRows - 1) / kPolRows), W::NW * 64, stream, N,
+                  obs, pool, member, pool_stride, K, pool_agent, J, max_action, P0, P1, obs_law, laws, k.k00, k.k01,
+                  k.k10, k.k11, env_offset, step, step_base, act0, logp0, act1, logp1);
+  });
+}
+
+int satrl_league_assign(uint64_t seed, uint64_t iteration, int64_t first_block, int64_t n_blocks, int K, int filled,
+                        int n_laws, double latest_prob, double law_prob, const double* weights,
+                        int32_t* member_out) {
+  if (!member_out) return fail(-1, __func__, "member_out is NULL");
+  if (n_blocks <= 0) return fail(-1, __func__, "n_blocks " + to_string(n_blocks) + " <= 0");
+  if (first_block < 0) return fail(-1, __func__, "first_block " + to_string(first_block) + " < 0");
+  if (K < 0) return fail(-1, __func__, "K " + to_string(K) + " < 0");
+  if (filled < 0 || filled > K)
+    return fail(-1, __func__, "filled " + to_string(filled) + " is outside 0 .. K = " + to_string(K));
+  if (n_laws < 0 || n_laws > SATRL_LEAGUE_MAX_LAWS)
+    return fail(-1, __func__, "n_laws " + to_string(n_laws) + " is outside 0 .. " + to_string(SATRL_LEAGUE_MAX_LAWS));
+  if (!(latest_prob >= 0.0 && latest_prob <= 1.0)) return fail(-1, __func__, "latest_prob is outside [0, 1]");
+  if (!(law_prob >= 0.0 && law_prob <= 1.0)) return fail(-1, __func__, "law_prob is outside [0, 1]");
+  const double law_edge = latest_prob + law_prob;
+  if (!(law_edge <= 1.0)) return fail(-1, __func__, "latest_prob + law_prob is above 1");
+  double S = 0.0;
+  int last_pos = -1;
+  if (weights && filled > 0) {
+    for (int k = 0; k < filled; ++k) {
+      if (!(weights[k] >= 0.0) || !std::isfinite(weights[k]))
+        return fail(-1, __func__, "weights[" + to_string(k) + "] is negative or not finite");
+      S += weights[k];
+      if (weights[k] > 0.0) last_pos = k;
+    }
+    if (!(S > 0.0) || !std::isfinite(S)) return fail(-1, __func__, "the sum of weights is not positive and finite");
+  }
+  uint32_t k0, k1;
+  philox_key(seed, 3, k0, k1);
+  for (int64_t i = 0; i < n_blocks; ++i) {
+    const uint64_t g = (uint64_t)first_block + (uint64_t)i;
+    uint32_t w[4] = {(uint32_t)g, (uint32_t)(g >> 32), (uint32_t)iteration, (uint32_t)(iteration >> 32)};
+    philox4x32_10(w, k0, k1);
+    const double u = ((double)w[0] + 0.5) * (1.0 / 4294967296.0);
+    int32_t m;
+    if ((filled == 0 && n_laws == 0) || u < latest_prob) {
+      m = -1;
+    } else if (n_laws > 0 && (filled == 0 || u < law_edge)) {
+      m = K + (int32_t)(((uint64_t)w[2] * (uint64_t)n_laws) >> 32);
+    } else if (!weights) {
+      m = (int32_t)(((uint64_t)w[1] * (uint64_t)filled) >> 32);
+    } else {
+      const double v = ((double)w[1] + 0.5) * (1.0 / 4294967296.0) * S;
+      double c = 0.0;
+      m = last_pos;
+      for (int k = 0; k < filled; ++k) {
+        c += weights[k];
+        if (v < c) {
+          m = k;
+          break;
+        }
+      }
+    }
+    member_out[i] = m;
   }
   return 0;
 }

@@ -37,6 +37,38 @@ __global__ void __launch_bounds__(256) gae_kernel(int64_t T, int64_t N, const fl
   }
 }
 
+// League tally (satrl_league_tally): finished episodes and captures of a
+// rollout per 32-env block.  One lane per env scans T in gae_kernel's shape
+// (coalesced across envs, the unrolled loop keeps several rows in flight);
+// lanes past N count nothing and stay for the reduction.  A block is one half
+// of a wave: five xor shuffles below 32 add its lanes, and the half's first
+// lane adds to the block's two words -- integers, no atomics, no order.
+__global__ void __launch_bounds__(64) league_tally_kernel(int64_t T, int64_t N, const float* __restrict__ rew,
+                                                          const uint8_t* __restrict__ done, float capture_reward,
+                                                          int64_t* __restrict__ tally) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  int ep = 0, cap = 0;                                            // (T * 1 per lane: the host refuses T above 2^31 - 1)
+  if (i < N) {
+#pragma unroll 8
+    for (int64_t t = 0; t < T; ++t) {
+      const int64_t o = t * N + i;
+      const int d = done[o] != 0;
+      ep += d;
+      cap += d & (int)(rew[o] == capture_reward);
+    }
+  }
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) {
+    ep += __shfl_xor(ep, off, 64);
+    cap += __shfl_xor(cap, off, 64);
+  }
+  if ((threadIdx.x & 31) == 0 && i < N) {
+    int64_t* w = tally + (i >> 5) * 2;
+    w[0] += ep;
+    w[1] += cap;
+  }
+}
+
 // choose_action (ppo_continuous.py:184-188): a = clamp(mean + std*z, +-max);
 // log_prob(a) per dim as torch.distributions.Normal.log_prob.  Noise:
 // philox_device.h, keyed by (seed, agent, global env id, step).
@@ -397,6 +429,15 @@ int satrl_gae(int64_t T, int64_t N, const float* r, const uint8_t* done, const f
   const int block = 64;   // N = 16384 envs -> 256 single-wave workgroups, one per CU
   return launch(__func__, gae_kernel, (N + block - 1) / block, block, stream, T, N, r, done, v, gamma, c, adv_out,
                 vtarget_out);
+}
+
+int satrl_league_tally(int64_t T, int64_t N, const float* rew, const uint8_t* done, float capture_reward,
+                       int64_t* tally, void* stream) {
+  if (int rc = positive(__func__, "T", T)) return rc;
+  if (int rc = positive(__func__, "N", N)) return rc;
+  if (T > INT32_MAX) return fail(-1, __func__, "T is above what a lane's 32-bit count holds");
+  if (int rc = null_arg(__func__, SATRL_PTRS(rew, done, tally))) return rc;
+  return launch(__func__, league_tally_kernel, (N + 63) / 64, 64, stream, T, N, rew, done, capture_reward, tally);
 }
 
 int satrl_gaussian_sample(int64_t N, const float* mean, const float* log_std, float max_action, uint64_t seed,

@@ -144,6 +144,7 @@ _SIGS = {
     "satrl_return_scan": ([_i64, _i64, _vp, _vp, C.c_double, _vp, _vp, _vp], C.c_int),
     "satrl_episode_record_reset": ([_i64, _vp, _vp, _vp, _vp], C.c_int),
     "satrl_episode_record": ([_i64, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp], C.c_int),
+    "satrl_league_tally": ([_i64, _i64, _vp, _vp, C.c_float, _vp, _vp], C.c_int),
     "satrl_last_error": ([], C.c_char_p),
     "satrl_ppo_layout": ([C.c_int, C.POINTER(_i64)], C.c_int),
     "satrl_ppo_sizes": ([C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)], C.c_int),
@@ -191,6 +192,10 @@ _SIGS = {
     "satrl_policy_act_pool": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_uint64, _i64, C.c_uint64, _vp, _vp, _vp,
                                _vp, _vp, C.c_int, _vp, _i64, C.c_int, _vp, _vp], C.c_int),
     "satrl_opponent_assign": ([C.c_uint64, C.c_uint64, _i64, _i64, C.c_int, C.c_double, _vp], C.c_int),
+    "satrl_policy_act_league": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_uint64, _i64, C.c_uint64, _vp, _vp, _vp,
+                                 _vp, _vp, C.c_int, _vp, _i64, C.c_int, _vp, _vp, _vp, C.c_int, _vp], C.c_int),
+    "satrl_league_assign": ([C.c_uint64, C.c_uint64, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                             _vp, _vp], C.c_int),
     "satrl_policy_eval": ([C.c_int, _i64, _vp, _vp, _vp, C.c_float, C.c_int, C.c_uint64, _i64, C.c_uint64, _vp, _vp,
                            _vp, _vp], C.c_int),
     "satrl_scripted_act": ([_i64, _vp, _vp, _vp, _vp], C.c_int),

@@ -38,6 +38,55 @@ def opponent_assign(seed, iteration, first_block, n_blocks, filled, latest_prob)
     return out
 
 
+def league_assign(seed, iteration, first_block, n_blocks, K, filled, n_laws, latest_prob, law_prob, weights=None):
+    """satrl_league_assign -> host int32 array [n_blocks]: -1 the live
+    opponent, k < K a stored slot, K + j law j.  weights: None (a uniform
+    stored pick, satrl_opponent_assign's) or f64 [filled]."""
+    out = np.empty(max(int(n_blocks), 0), dtype=np.int32)
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (int(filled),):
+            raise ValueError(f"weights holds one f64 per filled slot ({filled}), got {w.shape}")
+    check(_lib.lib().satrl_league_assign(int(seed) & (2**64 - 1), int(iteration) & (2**64 - 1), int(first_block),
+                                         int(n_blocks), int(K), int(filled), int(n_laws), float(latest_prob),
+                                         float(law_prob), None if w is None else w.ctypes.data_as(C.c_void_p),
+                                         out.ctypes.data_as(C.c_void_p)), "satrl_league_assign")
+    return out
+
+
+def pfsp_weights(episodes, wins, power=2):
+    """Prioritised fictitious self-play weights of stored opponents, f64: with
+    the learner's smoothed win rate p_k = (wins_k + 1) / (episodes_k + 2)
+    against slot k, weight_k = (1 - p_k) ** power by repeated multiplication
+    (play more often what you lose to).  An unplayed slot gets (1/2) ** power."""
+    if isinstance(power, bool) or int(power) != power or int(power) <= 0:
+        raise ValueError(f"pfsp_power is a positive int, got {power!r}")
+    e = np.asarray(episodes, dtype=np.float64)
+    w = np.asarray(wins, dtype=np.float64)
+    if e.shape != w.shape or e.ndim != 1 or (w < 0).any() or (w > e).any():
+        raise ValueError("episodes and wins are equal-length counts with 0 <= wins <= episodes")
+    base = 1.0 - (w + 1.0) / (e + 2.0)
+    out = base.copy()
+    for _ in range(int(power) - 1):
+        out = out * base
+    return out
+
+
+def league_tally(rew, done, capture_reward, tally):
+    """satrl_league_tally: tally i64 [ceil(N / 32), 2] += per 32-env block the
+    done steps of rew / done [T, N] and those whose reward is capture_reward."""
+    T, N = rew.shape
+    _lib.require_cuda(rew, torch.float32, (T, N), "rew")
+    if done.dtype == torch.bool:
+        done = done.view(torch.uint8)
+    _lib.require_cuda(done, torch.uint8, (T, N), "done")
+    _lib.require_cuda(tally, torch.int64, ((N + BLOCK - 1) // BLOCK, 2), "tally")
+    check(_lib.lib().satrl_league_tally(T, N, _lib.ptr(rew), _lib.ptr(done), float(capture_reward), _lib.ptr(tally),
+                                        _lib.stream_ptr()), "satrl_league_tally")
+    return tally
+
+
 class OpponentPool:
     """K ring slots of flat parameter sets of width H on `device`."""
 

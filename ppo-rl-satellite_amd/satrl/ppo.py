@@ -172,6 +172,40 @@ def policy_act_pool(H, obs, P0, P1, max_action, seed, env_offset, step, act0, lo
                                            int(stride), int(K), ptr(member), stream_ptr()), "satrl_policy_act_pool")
 
 
+def policy_act_league(H, obs, obs_law, P0, P1, max_action, seed, env_offset, step, act0, logp0, act1, logp1,
+                      pool_agent, pool, member, laws, J=None, step_base=None):
+    """policy_act_pool with a law table (satrl_policy_act_league): block b of
+    agent pool_agent acts with row member[b] of pool where 0 <= member[b] < K,
+    with law member[b] - K of `laws` (f64 [rows >= J, 58] on the device, a
+    satrl.scripted.LawTable's storage; J defaults to its rows) over the raw
+    observation obs_law where K <= member[b] < K + J, writing +0.0 log-probs,
+    and with its live parameters for every other value.  pool, member and laws
+    are read at every launch."""
+    N = obs.shape[0]
+    _lib.require_cuda(obs, torch.float32, (N, 18), "obs")
+    _lib.require_cuda(obs_law, torch.float32, (N, 18), "obs_law")
+    for t, nm in ((act0, "act0"), (logp0, "logp0"), (act1, "act1"), (logp1, "logp1")):
+        _lib.require_cuda(t, torch.float32, (N, 3), nm)
+    if pool.dim() != 2:
+        raise ValueError(f"pool must be [K, stride], got {tuple(pool.shape)}")
+    K, stride = pool.shape
+    _lib.require_cuda(pool, torch.float32, (K, stride), "pool")
+    _lib.require_cuda(member, torch.int32, ((N + 31) // 32,), "member")
+    if not torch.is_tensor(laws):
+        laws = laws.storage                                # a LawTable
+    if laws.dim() != 2:
+        raise ValueError(f"laws must be [J, 58], got {tuple(laws.shape)}")
+    _lib.require_cuda(laws, torch.float64, (laws.shape[0], 58), "laws")
+    J = laws.shape[0] if J is None else int(J)
+    if J > laws.shape[0]:
+        raise ValueError(f"J = {J} laws of a table of {laws.shape[0]} rows")
+    check(_lib.lib().satrl_policy_act_league(int(H), N, ptr(obs), ptr(P0), ptr(P1), float(max_action),
+                                             int(seed) & (2**64 - 1), int(env_offset), int(step), ptr(step_base),
+                                             ptr(act0), ptr(logp0), ptr(act1), ptr(logp1), int(pool_agent), ptr(pool),
+                                             int(stride), int(K), ptr(member), ptr(obs_law), ptr(laws), J,
+                                             stream_ptr()), "satrl_policy_act_league")
+
+
 def _law_block(law, device):
     """The device block (f64 [58]) of a satrl.scripted.ScriptedLaw, or the tensor itself."""
     blk = law.block(device) if hasattr(law, "block") else law

@@ -66,6 +66,7 @@ class ScriptedLaw:
     def __init__(self, G, b=None, max_action=1.6):
         self.G, self.b, self.max_action = _checked(G, b, max_action)
         self._block = None                               # f64 [58] on the device, allocated at its first use
+        self._table = None                               # the LawTable whose row the block is a view of, if any
 
     # -- the device block -------------------------------------------------------------------
     def packed(self):
@@ -196,6 +197,87 @@ def parse_opponents(spec):
             raise ValueError(f"scripted_opponent names agents {AGENTS}, got {k!r}")
         if v is not None:
             out[k] = as_law(v)
+    return out
+
+
+# -- league play: several laws in one device table --------------------------------------------
+LEAGUE_MAX_LAWS = 8                                      # SATRL_LEAGUE_MAX_LAWS (include/satrl_ppo.h)
+LEAGUE_WEIGHTINGS = ("uniform", "pfsp")
+
+
+class LawTable:
+    """The law table of satrl_policy_act_league: one f64 tensor [capacity, 58]
+    on `device` that never moves, a satrl_scripted_law per row.  ``set``
+    copies each law's 58 doubles into its row and makes the law's device block
+    a view of that row, so ``ScriptedLaw.update`` on a league law keeps
+    writing in place and stream-ordered, and captured graphs follow it.  Rows
+    past the set laws are zero (no thrust) and never assigned.  A law lives in
+    one table at a time, and a law that already owns a device block (one that
+    a kernel or a captured graph elsewhere may read) is refused: hand the
+    table a copy.  A ``set`` may move a law to another row or detach it (its
+    next use then allocates a block of its own), so whoever captured a graph
+    on a league law's block outside the table's own launch drops that graph
+    after a ``set`` (VecTrainer.set_league_laws does, for its evaluators)."""
+
+    def __init__(self, device, capacity=LEAGUE_MAX_LAWS):
+        self.capacity = int(capacity)
+        if not 1 <= self.capacity <= LEAGUE_MAX_LAWS:
+            raise ValueError(f"a law table holds 1 .. {LEAGUE_MAX_LAWS} laws, got capacity={capacity}")
+        self.device = torch.device(device)
+        self.storage = torch.zeros((self.capacity, LAW_DOUBLES), dtype=torch.float64, device=self.device)
+        self.laws = []
+
+    def __len__(self):
+        return len(self.laws)
+
+    def set(self, laws):
+        laws = [as_law(x) for x in (laws or [])]
+        if len(laws) > self.capacity:
+            raise ValueError(f"at most {self.capacity} league laws per agent, got {len(laws)}")
+        if len({id(x) for x in laws}) != len(laws):
+            raise ValueError("the same ScriptedLaw object twice in one law table: pass a copy")
+        for law in laws:
+            if law._table is not None and law._table is not self:
+                raise ValueError("this ScriptedLaw is bound to another law table: pass a copy "
+                                 "(ScriptedLaw.from_state(law.state()))")
+            if law._table is None and law._block is not None:
+                raise ValueError("this ScriptedLaw already owns a device block that launches elsewhere may read: "
+                                 "pass a copy (ScriptedLaw.from_state(law.state()))")
+        for old in self.laws:                            # a detached law allocates a block of its own at its next use
+            old._block, old._table = None, None
+        self.storage.zero_()
+        for j, law in enumerate(laws):
+            self.storage[j].copy_(torch.from_numpy(law.packed()))
+            law._block, law._table = self.storage[j], self
+        self.laws = laws
+        return self
+
+
+def parse_league(spec):
+    """args_param(league_laws=...): None, or a mapping {"evader": [law, ...],
+    "pursuer": [...]} whose entries are a ScriptedLaw or a builder's name, at
+    most LEAGUE_MAX_LAWS per agent.  Returns {agent: [ScriptedLaw]} without
+    the agents that have none."""
+    if spec is None:
+        return {}
+    try:
+        items = dict(spec).items()
+    except (TypeError, ValueError):
+        raise ValueError(f"league_laws is None or a mapping over {AGENTS} of lists of laws, "
+                         f"got {type(spec).__name__}") from None
+    out = {}
+    for k, v in items:
+        if k not in AGENTS:
+            raise ValueError(f"league_laws names agents {AGENTS}, got {k!r}")
+        if v is None:
+            continue
+        if isinstance(v, (str, ScriptedLaw)):
+            v = [v]
+        laws = [as_law(x) for x in v]
+        if len(laws) > LEAGUE_MAX_LAWS:
+            raise ValueError(f"at most {LEAGUE_MAX_LAWS} league laws per agent, got {len(laws)} for {k!r}")
+        if laws:
+            out[k] = laws
     return out
 
 

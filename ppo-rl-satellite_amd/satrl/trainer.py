@@ -25,7 +25,11 @@
   between two iterations: a fresh process continues with the bits of the
   run that never stopped, satrl/checkpoint.py.  Opt-in (scripted_opponent):
   an agent acts, whenever it is the frozen one, with a linear guidance law
-  instead of its network, satrl/scripted.py.
+  instead of its network, satrl/scripted.py.  Opt-in (league_laws,
+  opponent_weighting): league play on top of the pool -- per 32-env block
+  the live opponent, a stored one or one of several laws in one launch,
+  per-member results tallied from the rollout itself (``league_table``) and
+  stored opponents drawn by them (PFSP), DESIGN.md 3.2.3.
 """
 from __future__ import annotations
 
@@ -40,8 +44,8 @@ from . import pool as _pool
 from . import scripted as _scripted
 from .buffer import ReplayBuffer, RolloutBuffer
 from .env import VecSatellites
-from .ppo import (PPO_continuous, PPOLearner, gae, gaussian_sample, moments, policy_act, policy_act_pool,
-                  policy_act_scripted, policy_value, reduce_diagnostics_sums)
+from .ppo import (PPO_continuous, PPOLearner, gae, gaussian_sample, moments, policy_act, policy_act_league,
+                  policy_act_pool, policy_act_scripted, policy_value, reduce_diagnostics_sums)
 
 
 class args_param:  # noqa: N801
@@ -58,7 +62,8 @@ class args_param:  # noqa: N801
                  obs_norm=False, reward_scaling=False, obs_clip=10.0, obs_norm_calib_steps=64,
                  diagnostics=False, diagnostics_rows=None, target_kl=None, reset_spread=None, reset_seed=None,
                  opponent_pool=0, opponent_latest_prob=0.5, opponent_snapshot_every=None, opponent_seed=None,
-                 scripted_opponent=None):
+                 scripted_opponent=None, league_laws=None, league_law_prob=0.25, opponent_weighting="uniform",
+                 pfsp_power=2):
         self.max_train_steps = max_train_steps
         self.evaluate_freq = evaluate_freq
         self.save_freq = save_freq
@@ -174,6 +179,32 @@ class args_param:  # noqa: N801
         if self.opponent_pool > 0 and self.scripted_opponent:
             raise ValueError("a scripted opponent and an opponent pool on the same agent are not supported "
                              "(opponent_pool stores both agents)")
+        # league play of the vectorised engine: on top of the opponent
+        # pool, league_laws = {"evader": [law, ...], "pursuer": [...]} (a ScriptedLaw or a
+        # builder's name each, at most 8 per agent) are laws the frozen agent may also play,
+        # per 32-env block: the live opponent with probability opponent_latest_prob, one of
+        # the agent's laws with probability league_law_prob, else a stored one.
+        # opponent_weighting "uniform" draws the stored one as the pool does; "pfsp" draws
+        # slot k with weight (1 - p_k) ** pfsp_power, p_k the learner's smoothed win rate
+        # against it in the rollouts so far (satrl/pool.py pfsp_weights)
+        self.league_laws = _scripted.parse_league(league_laws)
+        self.league_law_prob = float(league_law_prob)
+        self.opponent_weighting = opponent_weighting
+        self.pfsp_power = pfsp_power
+        if self.league_laws and self.opponent_pool <= 0:
+            raise ValueError("league_laws need opponent_pool > 0 (laws are league members beside the stored "
+                             "opponents); one law in place of an agent's network is scripted_opponent")
+        if not 0.0 <= self.league_law_prob <= 1.0:                       # (NaN fails both comparisons)
+            raise ValueError(f"league_law_prob must be in [0, 1], got {league_law_prob}")
+        if self.league_laws and self.opponent_latest_prob + self.league_law_prob > 1.0:
+            raise ValueError(f"opponent_latest_prob + league_law_prob must not exceed 1, got "
+                             f"{opponent_latest_prob} + {league_law_prob}")
+        if opponent_weighting not in _scripted.LEAGUE_WEIGHTINGS:
+            raise ValueError(f"opponent_weighting is one of {_scripted.LEAGUE_WEIGHTINGS}, got {opponent_weighting!r}")
+        if isinstance(pfsp_power, bool) or not isinstance(pfsp_power, int) or pfsp_power <= 0:
+            raise ValueError(f"pfsp_power is a positive int, got {pfsp_power!r}")
+        if opponent_weighting == "pfsp" and self.opponent_pool <= 0:
+            raise ValueError("opponent_weighting='pfsp' needs opponent_pool > 0")
         # set by the train_* functions from the env (CPPO_main.py:99-101)
         self.state_dim = 18
         self.action_dim = 3
@@ -470,6 +501,20 @@ class VecTrainer:
         self._n_blocks = (self.N + _pool.BLOCK - 1) // _pool.BLOCK
         self.member = torch.full((self._n_blocks,), -1, dtype=torch.int32, device=self.device)
         self.last_assignment = np.full(self._n_blocks, -1, dtype=np.int32)
+        # league play: per agent a law table that never moves, and the
+        # cumulative (episodes, captures) of the learner's rollouts against each member of
+        # that agent's league: row 0 the live opponent, 1 + k stored slot k, 1 + K + j law j
+        self.league_law_prob = float(getattr(args, "league_law_prob", 0.25))
+        self.opponent_weighting = getattr(args, "opponent_weighting", "uniform")
+        self.pfsp_power = int(getattr(args, "pfsp_power", 2))
+        self._league = {k: _scripted.LawTable(self.device) for k in _scripted.AGENTS}
+        self.league_counts = {k: np.zeros((1 + K + _scripted.LEAGUE_MAX_LAWS, 2), dtype=np.int64)
+                              for k in _scripted.AGENTS}
+        self._tally = torch.zeros((self._n_blocks, 2), dtype=torch.int64, device=self.device)
+        self._tally_pending = False
+        for agent, laws in dict(getattr(args, "league_laws", None) or {}).items():
+            # (copies: one args object may build several trainers, and a law lives in one table)
+            self.set_league_laws(agent, [_scripted.ScriptedLaw.from_state(x.state()) for x in laws])
 
     @property
     def frozen_agent(self):
@@ -478,12 +523,115 @@ class VecTrainer:
 
     def _assign_opponents(self):
         """This iteration's member of every local block, over the frozen
-        agent's pool: written into the member tensor in place and
-        stream-ordered (the captured rollout graphs read it on every replay)."""
-        a = self.pools[self.frozen_agent].assign(self.iteration_count, self.env_offset // _pool.BLOCK, self._n_blocks,
-                                                 self.opponent_latest_prob)
+        agent's pool (and, in league play, its laws): written into the member
+        tensor in place and stream-ordered (the captured rollout graphs read it
+        on every replay)."""
+        pool = self.pools[self.frozen_agent]
+        n_laws = len(self._league[self.frozen_agent])
+        first = self.env_offset // _pool.BLOCK
+        if n_laws or self.opponent_weighting == "pfsp":
+            w = self._pfsp_weights() if self.opponent_weighting == "pfsp" and pool.filled else None
+            a = _pool.league_assign(pool.seed, self.iteration_count, first, self._n_blocks, pool.K, pool.filled, n_laws,
+                                    self.opponent_latest_prob, self.league_law_prob if n_laws else 0.0, w)
+        else:
+            a = pool.assign(self.iteration_count, first, self._n_blocks, self.opponent_latest_prob)
         self.member.copy_(torch.from_numpy(a))
         self.last_assignment = a
+
+    # -- league play (DESIGN.md 3.2.3) -----------------------------------------------------
+    def league_laws(self, agent=None):
+        """The ScriptedLaw objects of `agent`'s (default: the frozen agent's)
+        league, in law order: ScriptedLaw.update on one of them is followed by
+        the captured rollout graphs."""
+        if self.pools is None:
+            raise ValueError("no league: build the trainer with args.opponent_pool > 0")
+        return list(self._league[self._league_agent(agent)].laws)
+
+    def _league_agent(self, agent):
+        agent = self.frozen_agent if agent is None else agent
+        if agent not in _scripted.AGENTS:
+            raise ValueError(f"agent is one of {_scripted.AGENTS}, got {agent!r}")
+        return agent
+
+    def set_league_laws(self, agent, laws):
+        """`agent`'s ("pursuer" | "evader") league laws: a list of ScriptedLaw
+        objects or builders' names, at most 8; an empty list or None detaches
+        them.  The laws' values go into the agent's law table in place and
+        their device blocks become rows of it.  The captured rollout graphs
+        are dropped only when the agent's law count goes between zero and
+        non-zero (the launch changes); the cumulative counts of the agent's
+        law members start again at zero.  A law that already owns a device
+        block (it was used elsewhere) is refused: pass a copy."""
+        if self.pools is None:
+            raise ValueError("league laws need an opponent pool (args.opponent_pool > 0); one law in place of an "
+                             "agent's network is set_scripted_opponent")
+        agent = self._league_agent(agent)
+        tab = self._league[agent]
+        had = len(tab)
+        laws = [laws] if isinstance(laws, (str, _scripted.ScriptedLaw)) else list(laws or [])
+        if laws and self.opponent_latest_prob + self.league_law_prob > 1.0:
+            raise ValueError(f"opponent_latest_prob + league_law_prob must not exceed 1, got "
+                             f"{self.opponent_latest_prob} + {self.league_law_prob}")
+        tab.set(laws)                                # (validates everything before it changes anything)
+        for ev in self._evaluators.values():         # their graphs hold law blocks that may have moved
+            ev._graphs.clear()
+            ev._laws.clear()
+        self.league_counts[agent][1 + self.pools[agent].K:] = 0
+        if bool(had) != bool(len(tab)):
+            self._graphs.clear()
+
+    def _learner_wins(self, counts):
+        """The learner's wins out of rows (episodes, captures): the pursuer's
+        are the captures, the evader's the episodes that ended otherwise."""
+        return counts[:, 1] if self.flag == 0 else counts[:, 0] - counts[:, 1]
+
+    def _pfsp_weights(self):
+        """PFSP weights of the frozen agent's filled slots from the counts of
+        the finished iterations: the same on every rank and for every sharding."""
+        pool = self.pools[self.frozen_agent]
+        c = self.league_counts[self.frozen_agent][1:1 + pool.filled]
+        return _pool.pfsp_weights(c[:, 0], self._learner_wins(c), self.pfsp_power)
+
+    def _run_tally(self):
+        """After a rollout: this iteration's (episodes, captures) per local
+        block, on the stream; finish_iteration folds them."""
+        from .evaluate import capture_reward_of
+        self._tally.zero_()
+        _pool.league_tally(self.buf.rew, self.buf.done, capture_reward_of(self.env._p, self.flag), self._tally)
+        self._tally_pending = True
+
+    def _fold_tally(self):
+        """The iteration's per-block counts, by last_assignment, into the
+        cumulative per-member counts of the frozen agent's league (summed over
+        ranks first: integers, exact)."""
+        K = self.pools[self.frozen_agent].K
+        rows = 1 + K + _scripted.LEAGUE_MAX_LAWS
+        a = self.last_assignment.astype(np.int64)
+        idx = np.where((a >= 0) & (a < rows - 1), a + 1, 0)
+        local = np.zeros((rows, 2), dtype=np.int64)
+        np.add.at(local, idx, self._tally.cpu().numpy())
+        if self.pg is not None:
+            local = _dist.sum_(torch.from_numpy(local).to(self.device), self.pg).cpu().numpy()
+        self.league_counts[self.frozen_agent] += local
+        self._tally_pending = False
+
+    def league_table(self, agent=None):
+        """The learner's rollout results against each member of `agent`'s
+        (default: the frozen agent's) league, cumulative over the finished
+        iterations: rows (member code, "live" | "stored" | "law", meta,
+        episodes, captures) for the live opponent (-1), every filled slot k
+        and every law (K + j).  A stored slot's counts start again when the
+        ring overwrites it."""
+        if self.pools is None:
+            raise ValueError("no league: build the trainer with args.opponent_pool > 0")
+        agent = self._league_agent(agent)
+        pool, c = self.pools[agent], self.league_counts[agent]
+        rows = [(-1, "live", {"agent": agent}, int(c[0, 0]), int(c[0, 1]))]
+        rows += [(k, "stored", dict(pool.metas[k] or {}), int(c[1 + k, 0]), int(c[1 + k, 1]))
+                 for k in range(pool.filled)]
+        rows += [(pool.K + j, "law", {"agent": agent, "law": j}, int(c[1 + pool.K + j, 0]), int(c[1 + pool.K + j, 1]))
+                 for j in range(len(self._league[agent]))]
+        return rows
 
     def snapshot_opponent(self, agent=None):
         """Store `agent`'s ("pursuer" | "evader"; default: the learner's)
@@ -497,8 +645,10 @@ class VecTrainer:
         if agent not in self.pools:
             raise ValueError("agent is 'pursuer' or 'evader'")
         L = self.pursuer if agent == "pursuer" else self.evader
-        return self.pools[agent].add(L.P, {"agent": agent, "iteration_count": self.iteration_count,
-                                           "episodes": self.episodes})
+        k = self.pools[agent].add(L.P, {"agent": agent, "iteration_count": self.iteration_count,
+                                        "episodes": self.episodes})
+        self.league_counts[agent][1 + k] = 0         # the ring overwrote the slot: its results were the old set's
+        return k
 
     def pool_state(self):
         """Both pools as CPU tensors with their metas and ring cursors."""
@@ -714,6 +864,11 @@ class VecTrainer:
         elif self.pools is None:
             policy_act(self.pursuer.H, obs_t, self.pursuer.P, self.evader.P, 1.6, self.seed, self.env_offset, t,
                        pa, plp, ea, elp, step_base=self.step_base)
+        elif len(self._league[self.frozen_agent]):   # ... with its member of the league: a stored set or a law
+            policy_act_league(self.pursuer.H, obs_t, self.obs_raw if self.obs_norm else obs_t, self.pursuer.P,
+                              self.evader.P, 1.6, self.seed, self.env_offset, t, pa, plp, ea, elp, 1 - self.flag,
+                              self.pools[self.frozen_agent].storage, self.member, self._league[self.frozen_agent],
+                              step_base=self.step_base)
         else:                                    # the frozen agent acts, per 32-env block, with its member of the pool
             policy_act_pool(self.pursuer.H, obs_t, self.pursuer.P, self.evader.P, 1.6, self.seed, self.env_offset, t,
                             pa, plp, ea, elp, 1 - self.flag, self.pools[self.frozen_agent].storage, self.member,
@@ -823,6 +978,8 @@ class VecTrainer:
         self.rollout_steps += self.T
         if self.obs_norm:
             self._obs_acc_rows += self.T * self.N
+        if self.pools is not None:
+            self._run_tally()
 
     # -- learning -----------------------------------------------------------------
     def compute_advantages(self, chunk_steps=64):
@@ -906,6 +1063,8 @@ class VecTrainer:
             self.buf.obs[0].copy_(self.buf.obs[self.T])
         st = _dist.sum_(self.env.stats, self.pg)
         self.episodes = float(st[0].item())
+        if self.pools is not None and self._tally_pending:
+            self._fold_tally()
         self.iteration_count += 1
         self._in_iteration = False
         return st.cpu().numpy()
@@ -948,6 +1107,11 @@ class VecTrainer:
                 d["pools"][k] = s
         if self._laws:                           # (optional: a run without laws writes what it always wrote)
             d["scripted"] = {k: law.state() for k, law in self._laws.items()}
+        if self.pools is not None:
+            d["league"] = {"law_prob": float(self.league_law_prob), "weighting": self.opponent_weighting,
+                           "power": int(self.pfsp_power),
+                           "laws": {k: [law.state() for law in t.laws] for k, t in self._league.items()},
+                           "counts": {k: c.copy() for k, c in self.league_counts.items()}}
         return d
 
     def load_state_dict(self, d):
@@ -1008,6 +1172,8 @@ class VecTrainer:
                                      max_action=float(np.asarray(st["max_action"]).item()))
             else:
                 self.set_scripted_opponent(k, _scripted.ScriptedLaw.from_state(saved_laws[k]))
+        if self.pools is not None:
+            self._load_league(d.get("league"))
         if "gen" in d:
             self.gen.set_state(torch.from_numpy(np.ascontiguousarray(d["gen"], dtype=np.uint8)))
         else:
@@ -1025,6 +1191,46 @@ class VecTrainer:
         self.evaluations = [(int(it), float(ep), dict(s)) for it, ep, s in d.get("evaluations", [])]
         self._in_iteration = False
         self._loaded = True
+
+    def _load_league(self, lg):
+        """The "league" entry of a state.  None (a state written before league
+        play): the laws, the law probability, the weighting and the power stay
+        what the trainer was built with, and the counts are zero.  Otherwise an
+        agent whose law count is the saved one takes the saved values in place,
+        so the captured graphs and the caller's law objects stay."""
+        if lg is None:
+            for c in self.league_counts.values():
+                c[:] = 0
+            self._tally_pending = False
+            return
+        weighting = lg.get("weighting", "uniform")
+        if weighting not in _scripted.LEAGUE_WEIGHTINGS:
+            raise ValueError(f"state 'league/weighting' is {weighting!r}, not one of {_scripted.LEAGUE_WEIGHTINGS}")
+        self.opponent_weighting = weighting
+        if "law_prob" in lg:
+            self.league_law_prob = float(np.asarray(lg["law_prob"]).item())
+        if "power" in lg:
+            self.pfsp_power = int(np.asarray(lg["power"]).item())
+        saved = lg.get("laws") or {}
+        for k in _scripted.AGENTS:
+            states, tab = list(saved.get(k) or []), self._league[k]
+            if len(states) == len(tab):
+                for law, st in zip(tab.laws, states):
+                    law.update(G=np.asarray(st["G"], dtype=np.float64), b=np.asarray(st["b"], dtype=np.float64),
+                               max_action=float(np.asarray(st["max_action"]).item()))
+            else:
+                self.set_league_laws(k, [_scripted.ScriptedLaw.from_state(st) for st in states])
+        for k in _scripted.AGENTS:
+            c = (lg.get("counts") or {}).get(k)
+            if c is None:
+                self.league_counts[k][:] = 0
+                continue
+            c = np.asarray(c)
+            if c.shape != self.league_counts[k].shape or c.dtype.kind not in "iu":
+                raise ValueError(f"state 'league/counts/{k}': {c.dtype} {c.shape} for int64 "
+                                 f"{self.league_counts[k].shape}")
+            self.league_counts[k][:] = c
+        self._tally_pending = False
 
     def save_checkpoint(self, path):
         """The whole state into the directory `path` (satrl/checkpoint.py): one
@@ -1129,11 +1335,16 @@ class VecTrainer:
     def evaluate_pool(self, **kw):
         """evaluate(opponent=k, **kw) against every filled slot of the frozen
         agent's pool, [(meta, summary)] in slot order: the learner's row of
-        the cross-play table."""
+        the cross-play table.  With league laws, a row per law of the frozen
+        agent follows (evaluate(opponent=law), meta {"agent", "law": j})."""
         if self.pools is None:
             raise ValueError("evaluate_pool needs an opponent pool (args.opponent_pool > 0)")
         pool = self.pools[self.frozen_agent]
-        return [(dict(pool.metas[k]), self.evaluate(opponent=k, **kw).summary()) for k in range(pool.filled)]
+        rows = [(dict(pool.metas[k]), self.evaluate(opponent=k, **kw).summary()) for k in range(pool.filled)]
+        # league play: then one row per law of the frozen agent, in law order
+        rows += [({"agent": self.frozen_agent, "law": j}, self.evaluate(opponent=law, **kw).summary())
+                 for j, law in enumerate(self._league[self.frozen_agent].laws)]
+        return rows
 
     def iteration(self, timers=None):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
