@@ -135,7 +135,10 @@ int satrl_ppo_adam(int H, int mb, int net, const double* nsq, const double* step
  * at H = 256 the rowpass splits it into bf16 planes in registers -- a
  * pre-split planes image measured slower).
  * satrl_ppo_w2x_sync builds it from P (net -1: both) -- after a load or any
- * write to fc2.weight outside satrl_ppo_adam.                               */
+ * write to fc2.weight outside satrl_ppo_adam.  The rowpass relies on the
+ * image being P's fc2.weight transposed: where it skips phase D
+ * (satrl_ppo_rowpass_dskip) it bounds the image's elements by the
+ * fc2.weight elements its forward pass loaded from P.                      */
 int64_t satrl_ppo_w2x_floats(int H);
 int satrl_ppo_w2x_sync(int H, int net, const float* P, void* W2X, void* stream);
 
@@ -223,6 +226,22 @@ int satrl_ppo_rowpass_error(int* err, double timeout_s, void* stream);
  * the form it was captured with).  Returns the previous mode; mode -1 only
  * queries; anything else -1.                                               */
 int satrl_ppo_rowpass_sync(int mode);
+/* A second development switch (A/B timing, and the tests' bitwise oracle),
+ * outside the declared ABI: whether a
+ * wave of that 32-row kernel, in either sync form, may skip phase D (dH1 =
+ * dZ2 W2) and phase E's products and store +0.0 to its [dW1 | db1] slab
+ * rows.  It does so only where every output byte is the full path's: its own
+ * 32 x 16 tile of tanh(fc1) is exactly +-1 (fc1 saturated, as with raw-metre
+ * observations: dZ1 = dH1 x 0), the block's states are finite, and the
+ * exponents of the block's dZ2 and of the net's fc2.weight bound dH1 to
+ * finite values.  0: phase D always runs; 1: the default.  Process-wide, read
+ * at launch (a captured graph keeps the mode it was captured with).  Returns
+ * the previous mode; mode -1 only queries; anything else -1 with a message
+ * that names it.  The library exports it as
+ *     int satrl_ppo_rowpass_dskip(int mode)
+ * for the package's helper (satrl.ppo.rowpass_dskip) and the tests; it is not
+ * declared here: a call with mode 0 succeeds and changes the process, which
+ * no entry point of this ABI does when every argument is zero.             */
 /* satrl_ppo_rowpass_kx on that 32-row kernel whatever the minibatch size (the
  * kernel tests' entry: one block, ragged blocks, either block placement), in
  * the form satrl_ppo_rowpass_sync selects: ceil(mb / 32) slabs of ptail / pw1

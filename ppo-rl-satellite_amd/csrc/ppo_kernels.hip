@@ -190,6 +190,13 @@ template <int H>
 inline constexpr bool kTanhArms = H == 256;
 template <int H, int R>
 inline constexpr bool kZeroSkip = H == 256 && R == 32;
+// The D skip (rowpass_kernel, "D skip"): phase E's zero test decided before
+// phase D, whose product a saturated fc1 multiplies by zero.  In the k-packed
+// kernel (both sync forms: the product's update step at H 256); the f32-rows
+// instantiation of the same width (satrl_ppo_rowpass) is not on the product's
+// path and keeps phase E's test alone.
+template <int H, int R, bool KX>
+inline constexpr bool kDSkip = kZeroSkip<H, R> && KX;
 
 // tanh_f32 of the N values a call site holds, in place, with the arm chosen
 // per wave: the MLP's activations are mostly of one kind over a whole wave --
@@ -449,10 +456,26 @@ __device__ __forceinline__ f4 mfma6(const s8v (&a)[3], const s8v (&bs)[3], f4 c)
   return mfma_bf16(a[0], bs[0], c);
 }
 // one 32-wide k chunk: A planes (registers) x B (f32, split here)
-template <int RT, int CT>
-__device__ __forceinline__ void mfma3_regs(const s8v (&a)[RT][3], const float4 (&b)[CT][2], f4 (&acc)[RT][CT]) {
+// BOR: *bor |= the raw f32 bits of every B element (two v_or3_b32 per float4;
+// the rowpass's phase B, for its D skip).  The empty asm pins the ORs to the
+// split that consumes the chunk: left to the scheduler they drift away from
+// it, the raw chunks stay live, and the 32-row kernel went from 102 VGPRs to
+// 128 and 84 B of scratch.
+template <int RT, int CT, bool BOR = false>
+__device__ __forceinline__ void mfma3_regs(const s8v (&a)[RT][3], const float4 (&b)[CT][2], f4 (&acc)[RT][CT],
+                                           unsigned* bor = nullptr) {
 #pragma unroll
   for (int t = 0; t < CT; ++t) {
+    if constexpr (BOR) {
+      unsigned o = *bor;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        o |= __float_as_uint(b[t][q].x) | __float_as_uint(b[t][q].y);
+        o |= __float_as_uint(b[t][q].z) | __float_as_uint(b[t][q].w);
+      }
+      asm volatile("" : "+v"(o));
+      *bor = o;
+    }
     s8v bs[3];
     split3x8(b[t], bs);
 #pragma unroll
@@ -478,9 +501,12 @@ constexpr int kADB3 = 1;          // A chunk buffers (2: the next chunk's LDS re
 struct NoChunkWait {
   __device__ __forceinline__ void operator()(int) const {}
 };
-template <int K, int LDP, int PS, int LDB, int RT, int CT, bool PRE = false, class Wait = NoChunkWait>
+// BOR: the OR of the B elements' bits goes into *bor (mfma3_regs)
+template <int K, int LDP, int PS, int LDB, int RT, int CT, bool PRE = false, bool BOR = false,
+          class Wait = NoChunkWait>
 __device__ __forceinline__ void mfma_rows3(const unsigned short* __restrict__ A, const float* __restrict__ B, int n0,
-                                           f4 (&acc)[RT][CT], const WPre<CT>* pre = nullptr, Wait wait = Wait()) {
+                                           f4 (&acc)[RT][CT], const WPre<CT>* pre = nullptr, Wait wait = Wait(),
+                                           unsigned* bor = nullptr) {
   constexpr int NC = K / 32;
   constexpr int BPD = kBPD3 < NC ? kBPD3 : NC, NB = BPD + 1;
   static_assert(!PRE || BPD >= kBPD, "early-issued chunks fit the ring");
@@ -516,7 +542,7 @@ __device__ __forceinline__ void mfma_rows3(const unsigned short* __restrict__ A,
       wait(c);
       a3_chunk<LDP, PS, RT>(ap + 32 * c, aa[0]);
     }
-    mfma3_regs<RT, CT>(aa[kADB3 == 2 ? c % 2 : 0], bb[c % NB], acc);
+    mfma3_regs<RT, CT, BOR>(aa[kADB3 == 2 ? c % 2 : 0], bb[c % NB], acc, bor);
   }
 }
 
@@ -691,9 +717,12 @@ __device__ __attribute__((aligned(128))) unsigned g_cs_err[32];
 // are no epochs and nothing carries over from launch to launch.
 // Dependency order, a DAG over (phase, wave) after the gather's barrier:
 //   A(w) -> B(v) chunk w/2, every v;  B(w) -> out(w);  out(all) -> head (wave 0);
-//   head -> tail(w), every w;  tail(w) -> D(v) chunk w/2, every v;  D(w) -> E(w).
+//   head -> tail(w), every w;  tail(w) -> D(v) chunk w/2, every v;  D(w) -> E(w);
+//   tail(all) -> decision(w) of a wave w that may skip D (rowpass_kernel, "D
+//   skip"): it waits for every dz bit, then runs D and E or neither.
 // A producer step (A, out, head, tail) waits only for steps to its left, never
-// for a consumer, and all NW waves of a workgroup are resident together, so
+// for a consumer (none waits for a D or a decision), and all NW waves of a
+// workgroup are resident together, so
 // every wait ends.  No global-memory hand-off, no wait on another workgroup,
 // no wait on vmcnt: the plane stores and early weight chunks stay in flight.
 // Every poll is bounded (kRpPollMax sleeps, tens of ms): on running out the
@@ -702,10 +731,34 @@ __device__ __attribute__((aligned(128))) unsigned g_cs_err[32];
 // The arithmetic, the chunk and MFMA order and every operand are the barrier
 // form's: every output bit is the same.
 // ---------------------------------------------------------------------------
+// wmag, dzmag (the D skip of the 32-row kernel, both sync forms): the OR of
+// the raw f32 bits of every fc2.weight element the workgroup's waves load in
+// phase B (together the net's whole fc2), and of every dZ2 value of the block.
+// A wave ORs its share in (rp_or_put) just before it publishes out / dz (or
+// arrives at the barrier that stands for them), so whoever has seen all of
+// out (of dz) reads the complete word.
 struct RpFlags {
-  unsigned h1, dz, out, dz3;
+  unsigned h1, dz, out, dz3, wmag, dzmag;
 };
+__device__ __forceinline__ void rp_flags_zero(RpFlags& f) {
+  if (threadIdx.x == 0) f = RpFlags{0u, 0u, 0u, 0u, 0u, 0u};
+}
 __device__ __forceinline__ unsigned rp_wave() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+// OR over the wave's 64 lanes, wave-uniform: DPP ORs along each 16-lane row
+// (row16_sum's permutations), then the four rows' first lanes
+__device__ __forceinline__ unsigned wave_or(unsigned v) {
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);
+  return (unsigned)(__builtin_amdgcn_readlane((int)v, 0) | __builtin_amdgcn_readlane((int)v, 16) |
+                    __builtin_amdgcn_readlane((int)v, 32) | __builtin_amdgcn_readlane((int)v, 48));
+}
+// the wave's OR of v into an RpFlags magnitude word: lane 0's LDS atomic
+__device__ __forceinline__ void rp_or_put(unsigned* word, unsigned v) {
+  const unsigned o = wave_or(v);
+  if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_or(word, o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 constexpr unsigned kRpPollMax = 1u << 19;
 
 // this wave's LDS writes have landed; then lane 0's LDS atomic (OR: a bit, else add 1)
@@ -753,15 +806,19 @@ struct RpBarrier {
   __device__ __forceinline__ NoChunkWait wait_h1() { return NoChunkWait(); }
   __device__ __forceinline__ NoChunkWait wait_dz() { return NoChunkWait(); }
 };
+// RpBarrier of a kernel that keeps the magnitude words (the D skip)
+struct RpBarrierMag : RpBarrier {
+  RpFlags& f;
+  __device__ __forceinline__ explicit RpBarrierMag(RpFlags& flags) : f(flags) {}
+  __device__ __forceinline__ void init() { rp_flags_zero(f); }
+};
 template <int NW, class Head>
 struct RpHandoff {
   static constexpr bool kHandoff = true;
   static_assert(NW == 16, "a 32-column chunk is two waves' tiles; 16 bits per word");
   RpFlags& f;
   Head head;                                                        // the head's constants (head_consts)
-  __device__ __forceinline__ void init() {
-    if (threadIdx.x == 0) f = RpFlags{0u, 0u, 0u, 0u};
-  }
+  __device__ __forceinline__ void init() { rp_flags_zero(f); }
   __device__ __forceinline__ void after_gather() { head(); }
   __device__ __forceinline__ void h1_written() { rp_publish<true>(&f.h1, 1u << rp_wave()); }
   __device__ __forceinline__ void out_written() { rp_publish<false>(&f.out, 1u); }
@@ -1140,6 +1197,28 @@ __device__ __forceinline__ void tail(const f4 (&acc)[RT][CT], const float (&w3)[
 // wave), stores +0.0 and skips them; 0 x inf / 0 x NaN keep the MFMA path and
 // its NaNs.
 // SKIP: the kernels that take the short cut (kZeroSkip), nfw their NFW words.
+// (phase_e_zero: the short cut's stores, +0.0 to the wave's [dW1|db1] slab
+// rows; rows_finite_all: the guard.  Both also serve the D skip, which
+// decides the same before phase D, rowpass_kernel.)
+template <int CT>
+__device__ __forceinline__ void phase_e_zero(float* pw, int n0) {
+  const int l = threadIdx.x & 63, li = l & 15, lg = l >> 4;
+#pragma unroll
+  for (int t = 0; t < CT; ++t)
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb) {
+      const int kp = 16 * hb + li;
+      if (kp < 20) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pw[(int64_t)(n0 + 16 * t + 4 * lg + j) * 20 + kp] = 0.0f;
+      }
+    }
+}
+// whether no wave of the block gathered a non-finite state value (wave-uniform)
+template <int NFW>
+__device__ __forceinline__ bool rows_finite_all(const unsigned* nfw) {
+  return __builtin_amdgcn_ballot_w64(nfw[threadIdx.x & 63 & (NFW - 1)] != 0u) == 0;
+}
 template <bool SKIP, int NFW, int RT, int CT, int LDS_S>
 __device__ __forceinline__ void phase_e(f4 (&acc)[RT][CT], const float (&h1)[RT][CT][4],
                                         const float (&S)[16 * RT][LDS_S], float* pw, int n0,
@@ -1155,18 +1234,8 @@ __device__ __forceinline__ void phase_e(f4 (&acc)[RT][CT], const float (&h1)[RT]
         acc[rt][t][j] = acc[rt][t][j] * (1.0f - h1[rt][t][j] * h1[rt][t][j]);
         nz |= __float_as_uint(acc[rt][t][j]);
       }
-  if (SKIP && __builtin_amdgcn_ballot_w64((nz & 0x7fffffffu) != 0u) == 0 &&
-      __builtin_amdgcn_ballot_w64(nfw[l & (NFW - 1)] != 0u) == 0) {
-#pragma unroll
-    for (int t = 0; t < CT; ++t)
-#pragma unroll
-      for (int hb = 0; hb < 2; ++hb) {
-        const int kp = 16 * hb + li;
-        if (kp < 20) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) pw[(int64_t)(n0 + 16 * t + 4 * lg + j) * 20 + kp] = 0.0f;
-        }
-      }
+  if (SKIP && __builtin_amdgcn_ballot_w64((nz & 0x7fffffffu) != 0u) == 0 && rows_finite_all<NFW>(nfw)) {
+    phase_e_zero<CT>(pw, n0);
     return;
   }
 #pragma unroll
@@ -1242,14 +1311,19 @@ struct MlpSmem {
 // B's are all out (the policy kernel, see there).  sync: how the phases wait
 // for each other (RpBarrier / RpHandoff above; with RpHandoff osum is complete
 // only after sync.wait_out(), which the caller issues where it reads osum).
-template <int H, int NW, int R, bool APRE, bool PRIO = false, class Gather, class Sync = RpBarrier>
+// WMAG (the rowpass's D skip): the OR of the fc2.weight bits this wave loads
+// in phase B goes into *wmag (RpFlags::wmag) before out is published.
+template <int H, int NW, int R, bool APRE, bool PRIO = false, bool WMAG = false, class Gather,
+          class Sync = RpBarrier>
 __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* __restrict__ P,
                                             int net, int nvalid,
                                             Gather gather, float* __restrict__ h1out,
                                             f4 (&acc)[R / 16][H / 16 / NW],
                                             float (&h1)[R / 16][H / 16 / NW][4],
                                             float (&w3)[H / 16 / NW][3],
-                                            unsigned (&h1w)[R / 16][H / 16 / NW][6], Sync sync = Sync()) {
+                                            unsigned (&h1w)[R / 16][H / 16 / NW][6], Sync sync = Sync(),
+                                            unsigned* wmag = nullptr) {
+  static_assert(!WMAG || kBf3<H>, "the weight bits are collected in mfma_rows3");
   constexpr int RT = R / 16, LDA = H + 4, CT = H / 16 / NW, LDS_S = 36, NT = NW * 64;
   static_assert(CT >= 1 && H % (16 * NW) == 0, "tile split");
   static_assert(!Sync::kHandoff || kBf3<H>, "the hand-off form waits inside mfma_rows3");
@@ -1349,9 +1423,10 @@ __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* 
   sync.h1_written();                                               // (stamp 1 in there, or in B's first wait)
 
   // ---- B: Z2 = H1 W2^T -------------------------------------------------------
+  unsigned wbits = 0u;
   if constexpr (kBf3<H>)
-    mfma_rows3<H, MlpSmem<H, NW, R>::LDP, MlpSmem<H, NW, R>::PS, H, RT, CT, true>(
-        sm.h1p, P + L.W2 + (int64_t)net * H * H, n0, acc, &preB, sync.wait_h1());
+    mfma_rows3<H, MlpSmem<H, NW, R>::LDP, MlpSmem<H, NW, R>::PS, H, RT, CT, true, WMAG>(
+        sm.h1p, P + L.W2 + (int64_t)net * H * H, n0, acc, &preB, sync.wait_h1(), &wbits);
   else
     mfma_rows<H, LDA, H, RT, CT, APRE>(&sm.h1s[0][0], P + L.W2 + (int64_t)net * H * H, n0, acc);
   if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
@@ -1359,6 +1434,7 @@ __device__ __forceinline__ void mlp_forward(MlpSmem<H, NW, R>& sm, const float* 
 
   // ---- C (forward part): fc2 tanh, output-layer dot products -----------------
   fc2_out_partials(acc, b2v, w3, net, li, lg, sm.osum, w * CT);
+  if constexpr (WMAG) rp_or_put(wmag, wbits);
   sync.out_written();
   PHASE_PROBE(3);
 }
@@ -1374,10 +1450,12 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
                                                       float max_action, float* __restrict__ ptail,
                                                       float* __restrict__ pw1, float* __restrict__ p2,
                                                       int S2, float* __restrict__ ratio_out, float inv_mb,
-                                                      unsigned long long* __restrict__ span) {
+                                                      int dskip, unsigned long long* __restrict__ span) {
   // (argument order: the 14 dwords up to dZ2g are preloaded into SGPRs at wave
   // launch -- everything the block's net, the first weight loads and the row
-  // gather need; the rest comes by s_load under them.  DESIGN.md 3.4)
+  // gather need; the rest comes by s_load under them.  DESIGN.md 3.4.
+  // dskip, the D skip's switch (satrl_ppo_rowpass_dskip), is the last argument
+  // of the launch, before the span pointer launch_span appends.)
   const unsigned long long span_t0 = SPAN ? satrl_span::now() : 0ull;   // (SPAN: the measurement instantiation)
   constexpr int RT = R / 16, LDA = H + 4, CT = H / 16 / NW, NT = NW * 64;
   static_assert(!FDW2 || R == 32, "the fused dW2 partial covers one 32-row block (dw2_kernel's chunk)");
@@ -1439,8 +1517,11 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   };
   // how the phases wait for each other (RpBarrier / RpHandoff)
   __shared__ RpFlags flags;
+  // the D skip (below, before phase D): the k-packed 32-row kernel, both sync forms
+  constexpr bool DSKIP = kDSkip<H, R, KX>;
   auto sync = [&] {
     if constexpr (HANDOFF) return rp_handoff<NW>(flags, [&] { head_consts<NT>(hls_d, hb3_d, hcs, hb3s); });
+    else if constexpr (DSKIP) return RpBarrierMag(flags);
     else return RpBarrier();
   }();
   // the fc2 operand image: the f32 W2^T
@@ -1451,9 +1532,9 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   // policy kernel -- in-graph step 18.2 against 18.4 us at configs[1]'s
   // mb 4096, 15.3 against 15.5 at 512; at H = 256 no gain, not set there)
   if constexpr (FDW2) __builtin_amdgcn_s_setprio(3);
-  mlp_forward<H, NW, R, true, FDW2>(sm, P, net, mb - r0, gather,
-                                   FDW2 || KX || BF3 ? nullptr : H1g + ((int64_t)net * mb + r0) * H, acc, h1, w3,
-                                   h1w, sync);
+    mlp_forward<H, NW, R, true, FDW2, DSKIP>(sm, P, net, mb - r0, gather,
+                                          FDW2 || KX || BF3 ? nullptr : H1g + ((int64_t)net * mb + r0) * H, acc, h1,
+                                          w3, h1w, sync, &flags.wmag);
   // (KX) the H1 planes: wave 0, which runs the loss head next, stores its
   // share after the head's barrier (hand-off), off the head's path; the
   // other waves now
@@ -1463,9 +1544,49 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
     if (w != 0) h1_kx<H, R, CT>(H1x, dZ2x, net, mb, r0, n0, h1w);
   }
   else if constexpr (BF3 && !FDW2) store_rows<R, CT>(H1g + ((int64_t)net * mb + r0) * H, H, n0, mb - r0, h1);
+  // ---- D skip (DSKIP; dskip: satrl_ppo_rowpass_dskip, 0 = phase D always runs) ----
+  // dH1 has one use, phase E's dZ1 = dH1 (1 - H1^2).  A wave skips phase D and
+  // phase E's MFMAs and stores +0.0 to its [dW1|db1] slab rows, the bytes the
+  // full path gives, if
+  //  (a) 1 - h^2 is +-0 for each of its own 32 x 16 H1 values (fc1 saturated:
+  //      tanh_big returned +-1 exactly) -- one OR and one ballot, known here;
+  //  (b) the block's gathered states are finite (nfw, phase E's guard: with a
+  //      non-finite state E's MFMAs give NaNs that need the real dZ1);
+  //  (c) dH1 is finite, shown without computing it.  With e_dz, e_w the biased
+  //      exponent fields of RpFlags::dzmag / wmag (ORs of raw bits, so each is
+  //      >= the field of every dZ2 value of the block / fc2.weight element of
+  //      the net; 255 if any is inf or NaN): |x| < 2^(e - 126) for every such
+  //      element, hence |s| <= 2^(e - 126) for each of its three bf16 splits
+  //      (round to nearest never passes the next power of two).  An element of
+  //      dH1 is the sum of at most 6 x 256 < 2^11 split products, each
+  //      <= 2^(e_dz + e_w - 252), so every partial sum in the MFMA chain is
+  //      <= 2^(11 + e_dz + e_w - 252), finite in f32 while e_dz + e_w <= 367.
+  //      The test is e_dz != 255, e_w != 255, e_dz + e_w <= 360.
+  //      (Phase D reads the W2X image where wmag saw P's fc2.weight: the image
+  //      is that weight's transpose, include/satrl_ppo.h.)
+  // Then dZ1 = finite x (+-0) = +-0 in every lane, and phase E's MFMAs add
+  // +-0 x finite onto a +0 accumulator: +0.0 (phase_e's short cut, measured).
+  // A wave for which (a) and (b) hold -- a candidate -- issues no early W2T
+  // chunks, and after its tail waits for every wave's dZ2 (hand-off form: all
+  // dz bits; barrier form: the barrier there is), reads the two words (wmag is
+  // complete: the head ran behind every wave's out, the tail behind the head)
+  // and, if (c) fails, issues the chunks then and runs D and E as every other
+  // wave.  It writes its dZ2 planes, tail partials and plane stores first, as
+  // every wave: others read them.  No wave waits for a skipping wave's D.
+  bool cand = false;                                               // (wave-uniform)
+  if constexpr (DSKIP) {
+    unsigned nz = 0u;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int t = 0; t < CT; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) nz |= __float_as_uint(1.0f - h1[rt][t][j] * h1[rt][t][j]);
+    cand = dskip != 0 && __builtin_amdgcn_ballot_w64((nz & 0x7fffffffu) != 0u) == 0 && rows_finite_all<NW>(nfw);
+  }
   // phase D's first W2T chunks go out now, under the loss head and the tail
   WPre<CT> preD;
-  mfma_rows_pre<H, CT>(W2T + (int64_t)net * H * H, n0, preD);
+  if (!cand) mfma_rows_pre<H, CT>(W2T + (int64_t)net * H * H, n0, preD);
 
   // ---- C: the net's loss and its gradient, dZ2 ---------------------------------
   float* tp = ptail + (int64_t)rb * L.tail;                         // tail-relative slab of this row block
@@ -1483,26 +1604,55 @@ __global__ void __launch_bounds__(NW * 64, NW * 64 / 256) rowpass_kernel(int mb,
   float d2v[RT][CT][4];
   unsigned d2w[RT][CT][6];                                         // (split-bf16) the split dZ2 words
   tail<H, RT, CT, LDP, PS>(acc, w3, dz3s, &dzs[0][0], dzp, d2v, d2w, tp, net, n0);
+  if constexpr (DSKIP) {                                               // (D skip) this wave's dZ2 bits, before dz
+    unsigned dzb = 0u;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int t = 0; t < CT; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dzb |= __float_as_uint(d2v[rt][t][j]);
+    rp_or_put(&flags.dzmag, dzb);
+  }
   if constexpr (HANDOFF) sync.dz_written();                            // (before the plane stores: they drain under D)
   if constexpr (KX)
     store_kx_w<H, R, CT, R == kRowsShort>(dZ2x + net * 3 * PLX, PLX, r0, n0, d2w);
   else if constexpr (!FDW2) store_rows<R, CT>(dZ2g + ((int64_t)net * mb + r0) * H, H, n0, mb - r0, d2v);
   if constexpr (!HANDOFF) sync.dz_written();                           // the barrier (stamp 5; hand-off: in D's first wait)
 
-  // ---- D: dH1 = dZ2 W2 -------------------------------------------------------
+  float* const pw = pw1 + (int64_t)rb * 2 * H * 20 + (int64_t)net * H * 20;   // this net's [dW1|db1] slab
+  bool skip = false;                                                   // (D skip) the candidate's decision, (c)
+  if constexpr (DSKIP) {
+    if (cand) {
+      if constexpr (HANDOFF) {
+        rp_wait(&flags.dz, (1u << NW) - 1u);                           // every wave's tail
+        PHASE_PROBE(5);
+      }
+      const unsigned e_dz = (rp_read(&flags.dzmag) >> 23) & 0xffu, e_w = (rp_read(&flags.wmag) >> 23) & 0xffu;
+      skip = e_dz != 255u && e_w != 255u && e_dz + e_w <= 360u;
+      if (!skip) mfma_rows_pre<H, CT>(W2T + (int64_t)net * H * H, n0, preD);
+    }
+  }
+  if (skip) {
+    PHASE_PROBE(6);
+    phase_e_zero<CT>(pw, n0);
+    PHASE_PROBE(7);
+  } else {
+    // ---- D: dH1 = dZ2 W2 -----------------------------------------------------
 #pragma unroll
-  for (int rt = 0; rt < RT; ++rt)
+    for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-    for (int t = 0; t < CT; ++t) acc[rt][t] = f4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (BF3)
-    mfma_rows3<H, LDP, PS, H, RT, CT, true>(dzp, W2T + (int64_t)net * H * H, n0, acc, &preD, sync.wait_dz());
-  else
-    mfma_rows<H, LDA, H, RT, CT, true, true>(&dzs[0][0], W2T + (int64_t)net * H * H, n0, acc, &preD);
-  PHASE_PROBE(6);
+      for (int t = 0; t < CT; ++t) acc[rt][t] = f4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (BF3)
+      mfma_rows3<H, LDP, PS, H, RT, CT, true>(dzp, W2T + (int64_t)net * H * H, n0, acc, &preD, sync.wait_dz());
+    else
+      mfma_rows<H, LDA, H, RT, CT, true, true>(&dzs[0][0], W2T + (int64_t)net * H * H, n0, acc, &preD);
+    PHASE_PROBE(6);
 
-  // ---- E: dZ1 = dH1 (1 - H1^2); [dW1 | db1][n][k'] = sum_r dZ1[r][n] S[r][k'] ----
-  phase_e<ESKIP, NW>(acc, h1, S, pw1 + (int64_t)rb * 2 * H * 20 + (int64_t)net * H * 20, n0, nfw);
-  PHASE_PROBE(7);
+    // ---- E: dZ1 = dH1 (1 - H1^2); [dW1 | db1][n][k'] = sum_r dZ1[r][n] S[r][k'] ----
+    phase_e<ESKIP, NW>(acc, h1, S, pw, n0, nfw);
+    PHASE_PROBE(7);
+  }
 
   // ---- F (FDW2, H <= 128): this block's dW2 partial = dZ2^T H1 over its rows ---
   // straight from the LDS images (dzs, h1s), written as split-K slab rb of
@@ -3345,6 +3495,13 @@ int satrl_ppo_layout(int H, int64_t* off) {
 #define SATRL_RP_SYNC_DEFAULT 1
 #endif
 static std::atomic<int> g_rp_sync{SATRL_RP_SYNC_DEFAULT};
+// whether a wave of that kernel (either sync form) may skip phase D
+// (satrl_ppo_rowpass_dskip; rowpass_kernel, "D skip"): read at launch, passed
+// as a kernel argument -- one instantiation serves both modes
+#ifndef SATRL_RP_DSKIP_DEFAULT
+#define SATRL_RP_DSKIP_DEFAULT 1
+#endif
+static std::atomic<int> g_rp_dskip{SATRL_RP_DSKIP_DEFAULT};
 
 // ---------------------------------------------------------------------------
 // The step plan (satrl_ppo_step_plan): which kernels step a minibatch and what
@@ -3466,7 +3623,7 @@ static int launch_rowpass(const char* who, int H, int mb, int net, const float* 
       satrl_span::take(satrl_span::kRowpass, cs ? (int64_t)gc.x * kCsWaves : (int64_t)g.x * nw);
   auto rp = [&](auto k) {
     launch_span(k.first, k.second, sp, g, dim3(nw * 64), stream, mb, net, src, idx, P, W2X, H1, dZ2, epsilon,
-                ent_coef, max_action, ptail, pw1, p2, nrb, ratio, inv_mb);
+                ent_coef, max_action, ptail, pw1, p2, nrb, ratio, inv_mb, g_rp_dskip.load(std::memory_order_relaxed));
   };
   with_width<kNW256>(H, [&](auto w) {
     using W = decltype(w);
@@ -3537,6 +3694,11 @@ int satrl_ppo_rowpass_kx32(int H, int mb, int net, const float* src, const int64
 int satrl_ppo_rowpass_sync(int mode) {
   if (int rc = outside(__func__, "mode", mode, -1, 1)) return rc;
   return mode < 0 ? g_rp_sync.load(std::memory_order_relaxed) : g_rp_sync.exchange(mode, std::memory_order_relaxed);
+}
+
+int satrl_ppo_rowpass_dskip(int mode) {
+  if (int rc = outside(__func__, "mode", mode, -1, 1)) return rc;
+  return mode < 0 ? g_rp_dskip.load(std::memory_order_relaxed) : g_rp_dskip.exchange(mode, std::memory_order_relaxed);
 }
 
 int satrl_ppo_rowpass_error(int* err, double timeout_s, void* stream) {

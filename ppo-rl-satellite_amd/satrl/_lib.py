@@ -3,7 +3,9 @@
 The library exports exactly the functions declared in ``include/satenv.h``,
 ``satenv_cpu.h``, ``satrl_rollout.h``, ``satrl_ppo.h`` and ``satrl_peer.h``
 (plain pointers, sizes and a ``void*`` hipStream_t); ``_SIGS`` restates their
-signatures.  A refused call returns a negative code and leaves
+signatures.  (One development switch beside them, ``satrl_ppo_rowpass_dskip``,
+is described in ``satrl_ppo.h`` but not declared, and bound where it is used,
+``satrl.ppo.rowpass_dskip``.)  A refused call returns a negative code and leaves
 ``"<entry point>: <reason>"`` in its ABI's error slot: one for ``satenv_*``,
 one for ``satenv_cpu_*`` and one shared by every ``satrl_*`` entry point
 (``check`` raises with it).  It is built in-tree by ``csrc/Makefile`` for

@@ -499,6 +499,26 @@ def rowpass_sync(mode=None):
     return prev
 
 
+def rowpass_dskip(mode=None):
+    """satrl_ppo_rowpass_dskip (described in include/satrl_ppo.h; exported by
+    the library but outside the declared ABI and _lib's table, so bound here),
+    a development switch:
+    whether a wave of the 32-row H = 256 k-packed rowpass (either sync form)
+    may skip phase D where a saturated fc1 makes its product unused, 0 never
+    (phase D always runs), 1 the product default (bitwise the same outputs).
+    Sets the process-wide mode (None: only queries) and returns the previous
+    one; a captured graph keeps the mode it was captured with."""
+    try:
+        fn = _lib.lib().satrl_ppo_rowpass_dskip
+    except AttributeError as e:
+        raise _lib.NativeError(f"{_lib.LIB_PATH} has no satrl_ppo_rowpass_dskip: it was not built from this tree") from e
+    fn.argtypes, fn.restype = [C.c_int], C.c_int
+    prev = fn(-1 if mode is None else int(mode))
+    if prev < 0:
+        raise ValueError(f"rowpass_dskip: mode {mode!r} is not 0 or 1")
+    return prev
+
+
 def uses_handoff(H, mb, B):
     """True when an update of B rows in minibatches of mb runs the hand-off
     form of the 32-row rowpass (the plan of its full or ragged-tail minibatch
