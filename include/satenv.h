@@ -184,6 +184,60 @@ int satenv_cpu_set_episode_index(struct satenv_cpu_env* h, const int32_t* in, vo
 int satenv_cpu_get_episode_return(const struct satenv_cpu_env* h, double* out, void* stream);
 int satenv_cpu_set_episode_return(struct satenv_cpu_env* h, const double* in, void* stream);
 
+/* Actuation noise (no reference counterpart: the reference executes every
+ * commanded delta-v to the last bit, and that stays the default).  A handle
+ * carries, per agent g (0 pursuer, 1 evader), the half-widths mag[g] of a
+ * thrust magnitude error and dir[g] of a pointing error.  While the noise is
+ * enabled, every step -- satenv_step and satenv_step_autoreset -- replaces
+ * agent g's action a (f32, after the step's clip to +-1.6) by the executed
+ *   a'[c] = clip((float)(s * a[c] + e[c])),   c = 0, 1, 2
+ *   s = 1 + mag[g] * z[0],   e[c] = (dir[g] * |a|) * z[1 + c]          (f64)
+ *   z[m] = 2 * ((w[m] + 0.5) * 2^-32) - 1 in (-1, 1)
+ * with w the four words of one Philox4x32-10 block, counter (lo32(gid),
+ * hi32(gid), ep, cnt), gid = env_offset + i, ep = the env's episode index when
+ * the step begins, cnt = the step count this step uses (the device counter +
+ * 1, or the caller's episode_count), keyed by (seed, stream 3 + g); |a| is the
+ * f64 norm of the widened components, and every product and sum is rounded
+ * once in the written order.  Everything after the clip reads a': the
+ * velocity increment, the danger-zone gating, the fuel charge (an over-burn
+ * costs fuel) and the reward terms of the pursuer's action.  What a caller
+ * stored as the action (and its log-prob) stays the commanded one.  A zero
+ * action stays zero (coasting is exact), and an agent whose two half-widths
+ * are 0 draws nothing and keeps its bits.  The errors are bounded uniforms on
+ * purpose: a Gaussian needs log / sincos, which the device's and the host's
+ * math libraries do not round alike, and the draw is the same bits on every
+ * step kernel, on the host build and for every sharding of the envs.
+ * satenv_set_act_noise copies *host into the handle's device block with a
+ * stream-ordered kernel, as satenv_set_reset_dist does, with the same rule
+ * for graphs: the step kernels that can perturb are instantiations of their
+ * own, the first enabling call switches the handle to them for good (they read
+ * `enabled` from the block), so only a graph captured BEFORE a handle's first
+ * enabling call has to be captured again.
+ * satenv_act_noise_host is the model alone, on host pointers: a_out = a' of
+ * a_in (taken as already clipped) for global env id gid -- host->env_offset
+ * is not added -- or a_in where host->enabled is 0.
+ * Null pointers, non-finite or negative half-widths, mag > 1 (the thrust
+ * direction must not flip) and an agent other than 0 / 1 return
+ * SATENV_ERR_ARG, with "<entry point>: <field> ..." in the error slot.       */
+typedef struct satenv_act_noise {
+    double   mag[2], dir[2];   /* half-widths per agent: relative magnitude (<= 1), pointing */
+    uint64_t seed;
+    int64_t  env_offset;       /* global env id of env 0 (data-parallel shards) */
+    int32_t  enabled;          /* 0: every action is executed exactly */
+    int32_t  reserved;
+} satenv_act_noise;
+int satenv_default_act_noise(satenv_act_noise* host);   /* all zero, enabled 0 */
+int satenv_set_act_noise(satenv_env* h, const satenv_act_noise* host, void* stream);
+int satenv_get_act_noise(const satenv_env* h, satenv_act_noise* host);
+int satenv_act_noise_host(const satenv_act_noise* host, int64_t gid, int32_t ep, int32_t cnt, int32_t agent,
+                          const float a_in[3], float a_out[3]);
+/* ... and on the host build's handle (host pointers, synchronous) */
+int satenv_cpu_default_act_noise(satenv_act_noise* host);
+int satenv_cpu_set_act_noise(struct satenv_cpu_env* h, const satenv_act_noise* host, void* stream);
+int satenv_cpu_get_act_noise(const struct satenv_cpu_env* h, satenv_act_noise* host);
+int satenv_cpu_act_noise_host(const satenv_act_noise* host, int64_t gid, int32_t ep, int32_t cnt, int32_t agent,
+                              const float a_in[3], float a_out[3]);
+
 /* Time_window_of_danger_zone(R0_c, V0_c, R0_t, V0_t, Delta_V_c=fuel)
  *   .calculate_number_of_hanger_area()   satellite_function.py:18-99,341-373
  * on n independent absolute states: states f64 [n][12] = R_c V_c R_t V_t,

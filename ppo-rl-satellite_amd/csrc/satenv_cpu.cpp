@@ -46,6 +46,8 @@ struct satenv_cpu_env {
   int32_t err = 0;
   ResetDist rd{};                   // the reset distribution as the step reads it
   satenv_reset_dist dist{};         // ... and as satenv_cpu_set_reset_dist was given it
+  ActNoise an{};                    // the actuation noise as the step reads it
+  satenv_act_noise noise{};         // ... and as satenv_cpu_set_act_noise was given it
 };
 
 namespace {
@@ -53,7 +55,7 @@ namespace {
 // step_lane for env i; st (may be null) = the four per-env stat planes [4][n]
 void step_env(satenv_cpu_env* h, const StepIO& io, int64_t i, bool autoreset, double* st) {
   StepStats s;
-  const int rc = step_lane<true, true>(h->prm, h->n, h->f64.data(), h->i32.data(), io, i, autoreset, s);
+  const int rc = step_lane<true, true, true>(h->prm, h->n, h->f64.data(), h->i32.data(), io, i, autoreset, s);
   if (rc) {
 #pragma omp critical(satenv_cpu_err)
     if (h->err == 0) h->err = rc;
@@ -123,7 +125,8 @@ int satenv_cpu_reset(satenv_cpu_env* h, int32_t flag, const uint8_t* env_mask, f
 int satenv_cpu_step(satenv_cpu_env* h, const float* pa, const float* ea, const int32_t* episode_count,
                     float* obs_out, double* obs64_out, double* reward_out, uint8_t* done_out, void* /*stream*/) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_cpu_step: null argument");
-  const StepIO io{pa, ea, episode_count, obs_out, obs64_out, reward_out, nullptr, done_out, nullptr, nullptr, &h->rd};
+  const StepIO io{pa, ea, episode_count, obs_out, obs64_out, reward_out, nullptr, done_out, nullptr, nullptr, &h->rd,
+                  &h->an};
 #pragma omp parallel for num_threads(h->threads) schedule(dynamic, 64)
   for (int64_t i = 0; i < h->n; ++i) step_env(h, io, i, false, nullptr);
   return SATENV_OK;
@@ -132,7 +135,8 @@ int satenv_cpu_step(satenv_cpu_env* h, const float* pa, const float* ea, const i
 int satenv_cpu_step_autoreset(satenv_cpu_env* h, const float* pa, const float* ea, float* obs_out,
                               float* reward_out, uint8_t* done_out, double* stats_out, void* /*stream*/) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_cpu_step_autoreset: null argument");
-  const StepIO io{pa, ea, nullptr, obs_out, nullptr, nullptr, reward_out, done_out, nullptr, nullptr, &h->rd};
+  const StepIO io{pa, ea, nullptr, obs_out, nullptr, nullptr, reward_out, done_out, nullptr, nullptr, &h->rd,
+                  &h->an};
   const int64_t n = h->n;
   std::vector<double> st;
   if (stats_out) st.assign((size_t)4 * n, 0.0);
@@ -188,6 +192,37 @@ int satenv_cpu_set_reset_dist(satenv_cpu_env* h, const satenv_reset_dist* d, voi
 int satenv_cpu_get_reset_dist(const satenv_cpu_env* h, satenv_reset_dist* d) {
   if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_cpu_get_reset_dist: null argument");
   *d = h->dist;
+  return SATENV_OK;
+}
+
+int satenv_cpu_default_act_noise(satenv_act_noise* d) {
+  if (!d) return fail(SATENV_ERR_ARG, "satenv_cpu_default_act_noise: null");
+  std::memset(d, 0, sizeof(*d));
+  return SATENV_OK;
+}
+
+int satenv_cpu_set_act_noise(satenv_cpu_env* h, const satenv_act_noise* d, void* /*stream*/) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_cpu_set_act_noise: null argument");
+  ActNoise an;
+  if (const char* bad = act_noise_pack(*d, an))
+    return fail(SATENV_ERR_ARG, std::string("satenv_cpu_set_act_noise: ") + bad);
+  h->an = an;
+  h->noise = *d;
+  h->noise.enabled = d->enabled != 0;
+  h->noise.reserved = 0;
+  return SATENV_OK;
+}
+
+int satenv_cpu_get_act_noise(const satenv_cpu_env* h, satenv_act_noise* d) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_cpu_get_act_noise: null argument");
+  *d = h->noise;
+  return SATENV_OK;
+}
+
+int satenv_cpu_act_noise_host(const satenv_act_noise* d, int64_t gid, int32_t ep, int32_t cnt, int32_t agent,
+                              const float a_in[3], float a_out[3]) {
+  if (const char* bad = act_noise_host(d, gid, ep, cnt, agent, a_in, a_out))
+    return fail(SATENV_ERR_ARG, std::string("satenv_cpu_act_noise_host: ") + bad);
   return SATENV_OK;
 }
 

@@ -73,14 +73,16 @@ __device__ __forceinline__ void wave_stats(double* stats, StepStats s) {
 // The step kernels share one signature (launch_step); only a SPAN instantiation uses its last argument.
 // DRAW: the autoreset draws the start from the handle's reset distribution (satenv_step.h reset_state);
 // the default instantiations, which handles that never enabled one launch, do not carry that code.
+// NOISE: step_begin perturbs the clipped actions by the handle's actuation noise (satenv_step.h
+// act_noise); instantiated with DRAW only, for the handles that enabled it once.
 // One lane per env, the count's four solves one after another (64-lane blocks):
-template <bool AUTORESET, bool RK45 = false, bool DRAW = false>
+template <bool AUTORESET, bool RK45 = false, bool DRAW = false, bool NOISE = false>
 __global__ void __launch_bounds__(64) step_kernel(const Params prm, int64_t n, double* __restrict__ f64,
                                                   int32_t* __restrict__ i32, StepIO io, unsigned long long*) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   StepStats s;
   if (i < n) {
-    const int rc = step_lane<RK45, DRAW>(prm, n, f64, i32, io, i, AUTORESET, s);
+    const int rc = step_lane<RK45, DRAW, NOISE>(prm, n, f64, i32, io, i, AUTORESET, s);
     if (rc) atomicCAS(io.err, 0, rc);
   }
   if (io.stats) wave_stats(io.stats, s);
@@ -90,11 +92,11 @@ __global__ void __launch_bounds__(64) step_kernel(const Params prm, int64_t n, d
 // count, which is their schedule.  Returns whether the step needs the count.
 // (Their tail stays spelled out, `if (!L.terminal) { count, reward } step_end`:
 // a shared lane_tail cost the wide kernel time, EXPERIMENTS.md.)
-template <bool RK45>
+template <bool RK45, bool NOISE>
 __device__ __forceinline__ bool lane_head(const Params& prm, int64_t n, const double* __restrict__ f64,
                                           const int32_t* __restrict__ i32, const StepIO& io, int64_t i,
                                           bool autoreset, Lane& L, StepStats& s) {
-  step_begin<RK45>(prm, n, f64, i32, io, i, autoreset, L, s);
+  step_begin<RK45, NOISE>(prm, n, f64, i32, io, i, autoreset, L, s);
   if (L.err) atomicCAS(io.err, 0, L.err);
   return !L.terminal;
 }
@@ -108,7 +110,7 @@ __device__ __forceinline__ bool lane_head(const Params& prm, int64_t n, const do
 // latency bound: 16384 envs are only 256 waves).  Bit-identical to
 // step_kernel: every problem runs the same hybrd1.
 constexpr int kSplitEnvs = 64;
-template <bool AUTORESET, bool RK45 = false, bool DRAW = false>
+template <bool AUTORESET, bool RK45 = false, bool DRAW = false, bool NOISE = false>
 __global__ void __launch_bounds__(256) step_kernel_split(const Params prm, int64_t n, double* __restrict__ f64,
                                                          int32_t* __restrict__ i32, StepIO io, unsigned long long*) {
   __shared__ double sA[4][kSplitEnvs], sSt[4][kSplitEnvs], sDvm[4][kSplitEnvs], sX[4][kSplitEnvs];
@@ -123,7 +125,7 @@ __global__ void __launch_bounds__(256) step_kernel_split(const Params prm, int64
   if (w == 0) {
     bool on[2] = {false, false};
     if (live) {
-      if (lane_head<RK45>(prm, n, f64, i32, io, i, AUTORESET, L, s)) {
+      if (lane_head<RK45, NOISE>(prm, n, f64, i32, io, i, AUTORESET, L, s)) {
         rc = dz_setup(prm, L.k, L.fuel_c, L.fcm, z);                     // :150, :317-332
         if (rc == 0) { on[0] = z.q[0].ok; on[1] = z.q[1].ok; }
       }
@@ -250,7 +252,7 @@ __device__ __forceinline__ RfSolve get_rf_problem(const WideSmem<E>& sm, int w, 
 // ENVS envs per workgroup (lanes >= ENVS of each wave idle): fewer envs per
 // wave put more waves, i.e. more independent dependency chains, on each SIMD
 // when N is small (the step is latency bound there); 64 at large N
-template <bool AUTORESET, int ENVS, bool SPAN = false, bool DRAW = false>
+template <bool AUTORESET, int ENVS, bool SPAN = false, bool DRAW = false, bool NOISE = false>
 __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_t n, double* __restrict__ f64,
                                                         int32_t* __restrict__ i32, StepIO io,
                                                         unsigned long long* __restrict__ span) {
@@ -267,7 +269,7 @@ __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_
   if (w == 0) {
     int live = 0;
     if (in_range) {
-      live = lane_head<false>(prm, n, f64, i32, io, i, AUTORESET, L, s) ? (1 | (L.p_zero ? 2 : 0)) : 0;
+      live = lane_head<false, NOISE>(prm, n, f64, i32, io, i, AUTORESET, L, s) ? (1 | (L.p_zero ? 2 : 0)) : 0;
 #pragma unroll
       for (int c = 0; c < 12; ++c) sm.k[c][lane] = L.k[c];     // (no put_lane(L) helper: EXPERIMENTS.md)
 #pragma unroll
@@ -374,6 +376,8 @@ __global__ void __launch_bounds__(256) reset_kernel(const Params prm, const Rese
 // satenv_set_reset_dist: the struct rides in the argument segment, one lane
 // writes it into the handle's block -- stream-ordered with the steps around it
 __global__ void set_reset_dist_kernel(const ResetDist d, ResetDist* __restrict__ dst) { *dst = d; }
+// satenv_set_act_noise: the same for the handle's actuation-noise block
+__global__ void set_act_noise_kernel(const ActNoise d, ActNoise* __restrict__ dst) { *dst = d; }
 
 __global__ void init_kernel(const Params prm, int64_t n, double* f64, int32_t* i32) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -676,6 +680,9 @@ struct satenv_env {
   ResetDist* rd = nullptr;          // the reset distribution as the kernels read it (device)
   satenv_reset_dist dist{};         // ... and as satenv_set_reset_dist was given it
   bool draw = false;                // a distribution was enabled once: launch the DRAW step kernels
+  ActNoise* an = nullptr;           // the actuation noise as the kernels read it (device)
+  satenv_act_noise noise{};         // ... and as satenv_set_act_noise was given it
+  bool noisy = false;               // noise was enabled once: launch the DRAW + NOISE step kernels
   int kind = 2;    // step_kernel_wide (2), step_kernel_split (1) or the one-lane step_kernel (0)
   int wide_envs = 64;   // envs per workgroup of the wide kernel (16 / 32 for A/B; fewer envs per
                         // workgroup measured no faster)
@@ -685,23 +692,24 @@ namespace {
 
 int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
-template <bool AR, bool DRAW>
+template <bool AR, bool DRAW, bool NOISE>
 void launch_step_draw(satenv_env* h, const StepIO& io, void* stream) {
-  void (*plain)(const Params, int64_t, double*, int32_t*, StepIO, unsigned long long*) = step_kernel<AR, false, DRAW>;
+  void (*plain)(const Params, int64_t, double*, int32_t*, StepIO, unsigned long long*) =
+      step_kernel<AR, false, DRAW, NOISE>;
   decltype(plain) probed = nullptr;
   int envs = 64, threads = 256;   // per workgroup
   if (h->prm.propagator == 2) {   // the RK45 instantiation (its registers stay out of the STM kernels)
-    plain = step_kernel_split<AR, true, DRAW>;
+    plain = step_kernel_split<AR, true, DRAW, NOISE>;
   } else if (h->kind == 2) {
     envs = h->wide_envs;
-    plain = envs == 16   ? step_kernel_wide<AR, 16, false, DRAW>
-            : envs == 32 ? step_kernel_wide<AR, 32, false, DRAW>
-                         : step_kernel_wide<AR, 64, false, DRAW>;
+    plain = envs == 16   ? step_kernel_wide<AR, 16, false, DRAW, NOISE>
+            : envs == 32 ? step_kernel_wide<AR, 32, false, DRAW, NOISE>
+                         : step_kernel_wide<AR, 64, false, DRAW, NOISE>;
     // the product geometry (64 envs per workgroup) has a SPAN instantiation
     // for the bench's live launch spans (span_probe.h)
-    if (envs == 64) probed = step_kernel_wide<AR, 64, true, DRAW>;
+    if (envs == 64) probed = step_kernel_wide<AR, 64, true, DRAW, NOISE>;
   } else if (h->kind == 1) {
-    plain = step_kernel_split<AR, false, DRAW>;
+    plain = step_kernel_split<AR, false, DRAW, NOISE>;
   } else {
     threads = 64;
   }
@@ -710,11 +718,13 @@ void launch_step_draw(satenv_env* h, const StepIO& io, void* stream) {
   satrl_span::launch_span(probed, plain, sp, grid, dim3(threads), stream, h->prm, h->n, h->f64, h->i32, io);
 }
 
-// only an autoreset step resets, so only it has DRAW instantiations
+// only an autoreset step resets, so only it has DRAW instantiations of its own; the NOISE
+// ones are <DRAW, NOISE> for both (a step without autoreset never reaches the draw)
 template <bool AR>
 void launch_step(satenv_env* h, const StepIO& io, void* stream) {
-  if (AR && h->draw) launch_step_draw<AR, AR>(h, io, stream);
-  else launch_step_draw<AR, false>(h, io, stream);
+  if (h->noisy) launch_step_draw<AR, true, true>(h, io, stream);
+  else if (AR && h->draw) launch_step_draw<AR, AR, false>(h, io, stream);
+  else launch_step_draw<AR, false, false>(h, io, stream);
 }
 
 }  // namespace
@@ -796,6 +806,10 @@ int satenv_create(satenv_env** out, int64_t num_envs, const satenv_params* p, in
   reset_dist_pack(h->dist, rd);
   if (e == hipSuccess) e = hipMalloc(&h->rd, sizeof(ResetDist));
   if (e == hipSuccess) e = hipMemcpy(h->rd, &rd, sizeof(ResetDist), hipMemcpyHostToDevice);
+  ActNoise an{};
+  act_noise_pack(h->noise, an);
+  if (e == hipSuccess) e = hipMalloc(&h->an, sizeof(ActNoise));
+  if (e == hipSuccess) e = hipMemcpy(h->an, &an, sizeof(ActNoise), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     satenv_destroy(h);
     return fail(SATENV_ERR_HIP, std::string("satenv_create: ") + hipGetErrorString(e));
@@ -818,6 +832,7 @@ int satenv_destroy(satenv_env* h) {
   if (h->i32) (void)hipFree(h->i32);
   if (h->err) (void)hipFree(h->err);
   if (h->rd) (void)hipFree(h->rd);
+  if (h->an) (void)hipFree(h->an);
   delete h;
   return SATENV_OK;
 }
@@ -849,7 +864,8 @@ int satenv_reset(satenv_env* h, int32_t flag, const uint8_t* env_mask, float* ob
 int satenv_step(satenv_env* h, const float* pa, const float* ea, const int32_t* episode_count, float* obs_out,
                 double* obs64_out, double* reward_out, uint8_t* done_out, void* stream) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_step: null argument");
-  StepIO io{pa, ea, episode_count, obs_out, obs64_out, reward_out, nullptr, done_out, nullptr, h->err, h->rd};
+  StepIO io{pa, ea, episode_count, obs_out, obs64_out, reward_out, nullptr, done_out, nullptr, h->err, h->rd,
+            h->an};
   launch_step<false>(h, io, stream);
   HIP_TRY(hipGetLastError());
   return SATENV_OK;
@@ -858,7 +874,8 @@ int satenv_step(satenv_env* h, const float* pa, const float* ea, const int32_t* 
 int satenv_step_autoreset(satenv_env* h, const float* pa, const float* ea, float* obs_out, float* reward_out,
                           uint8_t* done_out, double* stats_out, void* stream) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_step_autoreset: null argument");
-  StepIO io{pa, ea, nullptr, obs_out, nullptr, nullptr, reward_out, done_out, stats_out, h->err, h->rd};
+  StepIO io{pa, ea, nullptr, obs_out, nullptr, nullptr, reward_out, done_out, stats_out, h->err, h->rd,
+            h->an};
   launch_step<true>(h, io, stream);
   HIP_TRY(hipGetLastError());
   return SATENV_OK;
@@ -912,6 +929,39 @@ int satenv_set_reset_dist(satenv_env* h, const satenv_reset_dist* d, void* strea
 int satenv_get_reset_dist(const satenv_env* h, satenv_reset_dist* d) {
   if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_get_reset_dist: null argument");
   *d = h->dist;
+  return SATENV_OK;
+}
+
+int satenv_default_act_noise(satenv_act_noise* d) {
+  if (!d) return fail(SATENV_ERR_ARG, "satenv_default_act_noise: null");
+  std::memset(d, 0, sizeof(*d));
+  return SATENV_OK;
+}
+
+int satenv_set_act_noise(satenv_env* h, const satenv_act_noise* d, void* stream) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_set_act_noise: null argument");
+  ActNoise an;
+  if (const char* bad = act_noise_pack(*d, an))
+    return fail(SATENV_ERR_ARG, std::string("satenv_set_act_noise: ") + bad);
+  hipLaunchKernelGGL(set_act_noise_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, an, h->an);
+  HIP_TRY(hipGetLastError());
+  h->noise = *d;
+  h->noise.enabled = d->enabled != 0;
+  h->noise.reserved = 0;
+  if (d->enabled) h->noisy = true;   // from now on the NOISE step kernels, whatever the block says later
+  return SATENV_OK;
+}
+
+int satenv_get_act_noise(const satenv_env* h, satenv_act_noise* d) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_get_act_noise: null argument");
+  *d = h->noise;
+  return SATENV_OK;
+}
+
+int satenv_act_noise_host(const satenv_act_noise* d, int64_t gid, int32_t ep, int32_t cnt, int32_t agent,
+                          const float a_in[3], float a_out[3]) {
+  if (const char* bad = act_noise_host(d, gid, ep, cnt, agent, a_in, a_out))
+    return fail(SATENV_ERR_ARG, std::string("satenv_act_noise_host: ") + bad);
   return SATENV_OK;
 }
 

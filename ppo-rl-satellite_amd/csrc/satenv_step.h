@@ -21,6 +21,7 @@ constexpr int kI32Planes = 4;   // 3 public + per-env episode index
 constexpr int kPlaneRet = 15;
 constexpr int kPlaneDz = 0, kPlaneCount = 1, kPlaneBits = 2, kPlaneEp = 3;
 constexpr uint32_t kResetStream = 2;   // philox_key stream of the reset draw (0 / 1: the agents' action noise)
+constexpr uint32_t kActNoiseStream = 3;   // ... and of agent g's actuation noise: 3 + g
 
 struct alignas(8) F32x2 { float x, y; };
 
@@ -54,6 +55,40 @@ inline bool reset_dist_pack(const satenv_reset_dist& in, ResetDist& out) {
   return true;
 }
 
+// The handle's actuation noise as the kernels read it (satenv_act_noise,
+// include/satenv.h): per agent g (0 pursuer, 1 evader) the
+// half-widths of the thrust magnitude and pointing errors and the key of its
+// stream.  A block of its own beside the ResetDist, written by its own setter
+// launch and read where step_begin clips the actions.
+struct ActNoise {
+  double mag[2], dir[2];
+  uint32_t k0[2], k1[2];  // philox_key(seed, kActNoiseStream + g)
+  int64_t env_offset;     // global env id of env 0
+  int32_t enabled;
+  int32_t reserved;
+};
+
+// satenv_act_noise -> ActNoise; nullptr, or what is wrong with which field
+inline const char* act_noise_pack(const satenv_act_noise& in, ActNoise& out) {
+  static const char* const kBad[2][3] = {
+      {"mag[0] must be finite and >= 0", "dir[0] must be finite and >= 0",
+       "mag[0] must not exceed 1 (the thrust direction must not flip)"},
+      {"mag[1] must be finite and >= 0", "dir[1] must be finite and >= 0",
+       "mag[1] must not exceed 1 (the thrust direction must not flip)"}};
+  for (int g = 0; g < 2; ++g) {
+    if (!std::isfinite(in.mag[g]) || !(in.mag[g] >= 0.0)) return kBad[g][0];
+    if (!std::isfinite(in.dir[g]) || !(in.dir[g] >= 0.0)) return kBad[g][1];
+    if (in.mag[g] > 1.0) return kBad[g][2];
+    out.mag[g] = in.mag[g];
+    out.dir[g] = in.dir[g];
+    philox_key(in.seed, kActNoiseStream + (uint32_t)g, out.k0[g], out.k1[g]);
+  }
+  out.env_offset = in.env_offset;
+  out.enabled = in.enabled != 0;
+  out.reserved = 0;
+  return nullptr;
+}
+
 struct StepIO {
   const float* pa;
   const float* ea;
@@ -66,6 +101,7 @@ struct StepIO {
   double* stats;
   int32_t* err;
   const ResetDist* rd;        // the handle's reset distribution (never null)
+  const ActNoise* an;         // the handle's actuation noise (never null)
 };
 
 // one env's share of a step's statistics (step_autoreset's stats_out): episode
@@ -135,6 +171,46 @@ SATENV_HD void reset_draw(const ResetDist* d, int64_t i, uint32_t ep, double (&k
       k[4 * j + m] = rd_load(&d->lo[4 * j + m]) + rd_load(&d->span[4 * j + m]) * u;
     }
   }
+}
+
+// The action agent g's thrusters execute for the commanded (clipped) action a
+// of global env `gid` in step `cnt` of its episode `ep`:
+//   a'[c] = clip16((float)(s * a[c] + e[c])),  s = 1 + mag * z[0],
+//   e[c] = (dir * |a|) * z[1 + c],  z[m] = 2 * ((w[m] + 0.5) * 2^-32) - 1 in (-1, 1)
+// with w one Philox4x32-10 block, counter (gid, ep, cnt), key (seed, stream 3 +
+// g).  A magnitude error along the command plus an isotropic pointing error
+// that scales with it: a zero command stays zero, and mag <= 1 keeps s > 0.
+// Bounded uniforms on purpose: a Gaussian needs log / sincos, which are not
+// the same bits on OCML and glibc, and the draw has to be (integer rounds, an
+// exact u, then f64 products and sums each rounded once, no contraction; |a|
+// is norm3's fma chain over exact squares of widened f32, so it is too).  An
+// agent whose half-widths are both 0 draws nothing and keeps its bits.
+SATENV_HD void act_noise(const ActNoise* d, int g, uint64_t gid, uint32_t ep, uint32_t cnt, float (&a)[3]) {
+  const double mag = rd_load(&d->mag[g]), dir = rd_load(&d->dir[g]);
+  if (mag == 0.0 && dir == 0.0) return;
+  uint32_t w[4] = {(uint32_t)gid, (uint32_t)(gid >> 32), ep, cnt};
+  philox4x32_10(w, rd_load(&d->k0[g]), rd_load(&d->k1[g]));
+  double z[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) z[m] = 2.0 * (((double)w[m] + 0.5) * 0x1p-32) - 1.0;
+  const double s = 1.0 + mag * z[0];
+  const double r = dir * norm3((double)a[0], (double)a[1], (double)a[2]);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) a[c] = clip16((float)(s * (double)a[c] + r * z[1 + c]));
+}
+
+// satenv_act_noise_host and its satenv_cpu_ twin: the model on host pointers;
+// nullptr, or the refusal's reason
+inline const char* act_noise_host(const satenv_act_noise* in, int64_t gid, int32_t ep, int32_t cnt, int32_t agent,
+                                  const float* a_in, float* a_out) {
+  if (!in || !a_in || !a_out) return "null argument";
+  if (agent != 0 && agent != 1) return "agent must be 0 (pursuer) or 1 (evader)";
+  ActNoise d;
+  if (const char* bad = act_noise_pack(*in, d)) return bad;
+  float a[3] = {a_in[0], a_in[1], a_in[2]};
+  if (d.enabled) act_noise(&d, agent, (uint64_t)gid, (uint32_t)ep, (uint32_t)cnt, a);
+  for (int c = 0; c < 3; ++c) a_out[c] = a[c];
+  return nullptr;
 }
 
 // One reset of env i (the masked reset and the autoreset): the kinematics it
@@ -211,8 +287,9 @@ struct Lane {
 
 // kRk45: the instantiation that carries propagator 2 (solve_ivp RK45); the
 // default kernels leave it out so its registers do not cost the STM path
-// occupancy
-template <bool kRk45 = false>
+// occupancy.  kNoise: the instantiation of handles that enabled actuation
+// noise once; the others do not carry its code (as kDraw in reset_state).
+template <bool kRk45 = false, bool kNoise = false>
 SATENV_HD void step_begin(const Params& prm, int64_t n, const double* __restrict__ f64,
                                            const int32_t* __restrict__ i32, const StepIO& io, int64_t i,
                                            bool autoreset, Lane& L, StepStats& s) {
@@ -235,6 +312,14 @@ SATENV_HD void step_begin(const Params& prm, int64_t n, const double* __restrict
   for (int c = 0; c < 3; ++c) {
     L.pa[c] = clip16(io.pa[i * 3 + c]);                                  // :86-87
     ea[c] = clip16(io.ea[i * 3 + c]);
+  }
+  if constexpr (kNoise) {                                                 // from here on the env sees the
+    if (rd_load(&io.an->enabled)) {                                       // executed actions only
+      const uint64_t gid = (uint64_t)rd_load(&io.an->env_offset) + (uint64_t)i;
+      const uint32_t ep = (uint32_t)i32[kPlaneEp * n + i];
+      act_noise(io.an, 0, gid, ep, (uint32_t)L.count, L.pa);
+      act_noise(io.an, 1, gid, ep, (uint32_t)L.count, ea);
+    }
   }
   L.dis_prev = norm3(k[0] - k[6], k[1] - k[7], k[2] - k[8]);             // :89
   bool p_zero = false, e_zero = false, move_p = true, move_e = true;
@@ -383,11 +468,11 @@ SATENV_HD void step_end(const Params& prm, int64_t n, double* __restrict__ f64,
 // The whole step of env i in one lane (the count's four solves one after
 // another): the one-lane kernel and the host build.  Returns the error code
 // to record, 0 if none; the caller owns the (first-wins) error sink.
-template <bool kRk45, bool kDraw>
+template <bool kRk45, bool kDraw, bool kNoise = false>
 SATENV_HD int step_lane(const Params& prm, int64_t n, double* __restrict__ f64, int32_t* __restrict__ i32,
                         const StepIO& io, int64_t i, bool autoreset, StepStats& s) {
   Lane L;
-  step_begin<kRk45>(prm, n, f64, i32, io, i, autoreset, L, s);
+  step_begin<kRk45, kNoise>(prm, n, f64, i32, io, i, autoreset, L, s);
   int err = L.err;
   if (!L.terminal) {
     int cnt = 0;

@@ -51,6 +51,12 @@ class SatenvResetDist(C.Structure):
                 ("enabled", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SatenvActNoise(C.Structure):
+    """Mirror of ``satenv_act_noise`` (include/satenv.h)."""
+    _fields_ = [("mag", C.c_double * 2), ("dir", C.c_double * 2), ("seed", C.c_uint64), ("env_offset", C.c_int64),
+                ("enabled", C.c_int32), ("reserved", C.c_int32)]
+
+
 class StepPlan(C.Structure):
     """Mirror of ``satrl_ppo_plan`` (include/satrl_ppo.h)."""
     _fields_ = ([(k, C.c_int) for k in ("step", "rowpass", "rows_per_block", "row_blocks", "splits", "error_word")] +
@@ -123,6 +129,14 @@ _SIGS = {
     "satenv_cpu_get_reset_dist": ([_vp, C.POINTER(SatenvResetDist)], C.c_int),
     "satenv_cpu_get_episode_index": ([_vp, _vp, _vp], C.c_int),
     "satenv_cpu_set_episode_index": ([_vp, _vp, _vp], C.c_int),
+    "satenv_default_act_noise": ([C.POINTER(SatenvActNoise)], C.c_int),
+    "satenv_set_act_noise": ([_vp, C.POINTER(SatenvActNoise), _vp], C.c_int),
+    "satenv_get_act_noise": ([_vp, C.POINTER(SatenvActNoise)], C.c_int),
+    "satenv_act_noise_host": ([C.POINTER(SatenvActNoise), _i64, _i32, _i32, _i32, _vp, _vp], C.c_int),
+    "satenv_cpu_default_act_noise": ([C.POINTER(SatenvActNoise)], C.c_int),
+    "satenv_cpu_set_act_noise": ([_vp, C.POINTER(SatenvActNoise), _vp], C.c_int),
+    "satenv_cpu_get_act_noise": ([_vp, C.POINTER(SatenvActNoise)], C.c_int),
+    "satenv_cpu_act_noise_host": ([C.POINTER(SatenvActNoise), _i64, _i32, _i32, _i32, _vp, _vp], C.c_int),
     "satenv_cpu_last_error": ([], C.c_char_p),
     "satenv_cpu_create": ([C.POINTER(_vp), _i64, C.POINTER(SatenvParams), C.c_int], C.c_int),
     "satenv_cpu_destroy": ([_vp], C.c_int),

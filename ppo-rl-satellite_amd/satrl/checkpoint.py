@@ -35,7 +35,10 @@ PER_ENV = {"env/f64": 1, "env/i32": 1, "env/ep_return": 0, "env/episode_index": 
            "obs_raw": 0}
 
 # what must be equal between the writer and the reader (horizon, K_epochs, the
-# learning rates, the graph knobs and diagnostics may differ)
+# learning rates, the graph knobs and diagnostics may differ; the actuation
+# noise is not here either: its spec and seed are state, "act_noise", which the
+# reader takes over from rank 0's file whatever its own sharding -- the draw is
+# keyed by the global env id, the episode index and the step count, all restored)
 FINGERPRINT_FIELDS = ("hidden_width", "global_envs", "seed", "reset_seed", "opponent_seed", "obs_norm",
                       "reward_scaling", "opponent_pool", "minibatch_sampler", "dp_minibatch", "mini_batch_size",
                       "max_episode_steps", "d_capture", "reset_box", "max_train_steps")

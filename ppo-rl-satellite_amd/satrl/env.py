@@ -92,6 +92,36 @@ def reset_box(spread):
     return lo, hi
 
 
+def act_noise_spec(spec):
+    """args_param.act_noise -> ((mag, dir) of the pursuer, (mag, dir) of the
+    evader) as floats, or None for None: a pair (mag, dir) holds for both
+    agents, a dict {"pursuer": (mag, dir), "evader": (mag, dir)} for the agents
+    it names (the other one is exact).  mag: half-width of the relative thrust
+    magnitude error, at most 1; dir: half-width of the pointing error as a
+    fraction of the commanded |a| (include/satenv.h satenv_act_noise)."""
+    if spec is None:
+        return None
+
+    def pair(v, who):
+        try:
+            mag, dire = (float(x) for x in v)
+        except (TypeError, ValueError):
+            raise ValueError(f"act_noise: {who} is a pair (mag, dir) of numbers, got {v!r}") from None
+        if not (math.isfinite(mag) and math.isfinite(dire) and mag >= 0.0 and dire >= 0.0):
+            raise ValueError(f"act_noise: {who}'s half-widths must be finite and >= 0, got {v!r}")
+        if mag > 1.0:
+            raise ValueError(f"act_noise: {who}'s mag must not exceed 1 (the thrust must not flip), got {mag}")
+        return mag, dire
+
+    if isinstance(spec, dict):
+        unknown = set(spec) - {"pursuer", "evader"}
+        if unknown:
+            raise ValueError(f"act_noise: keys are 'pursuer' and 'evader', got {sorted(map(str, unknown))}")
+        return tuple(pair(spec[k], k) if k in spec else (0.0, 0.0) for k in ("pursuer", "evader"))
+    both = pair(spec, "the spec")
+    return both, both
+
+
 def _num_mode(v) -> int:
     if isinstance(v, np.float32):
         return F32
@@ -161,6 +191,7 @@ class VecSatellites:
         self.observation_space, self.action_space, self.action_space_beta = _spaces()
         self.stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         self.draws = False               # set_reset_dist was called: the handle launches the drawing step kernels
+        self.noisy = False               # set_act_noise was called: ... the step kernels with the actuation noise
 
     def _fn(self, name):
         return getattr(_lib.lib(), self._api + name)
@@ -323,6 +354,46 @@ class VecSatellites:
             return None
         return {"lo": np.array(d.lo[:]), "hi": np.array(d.hi[:]), "seed": int(d.seed), "env_offset": int(d.env_offset)}
 
+    # -- actuation noise (include/satenv.h satenv_act_noise) ---------------------
+    def _get_noise(self):
+        d = _lib.SatenvActNoise()
+        check(self._fn("get_act_noise")(self._h, C.byref(d)), self._api + "get_act_noise")
+        return d
+
+    def _set_noise(self, d):
+        check(self._fn("set_act_noise")(self._h, C.byref(d), self._sp()), self._api + "set_act_noise")
+
+    def set_act_noise(self, pursuer=(0.0, 0.0), evader=(0.0, 0.0), seed=0, env_offset: int = 0):
+        """From now on every step executes, for each agent, its clipped action
+        with a thrust magnitude error of relative half-width mag (<= 1) and a
+        pointing error of half-width dir * |a|, pursuer=(mag, dir) and
+        evader=(mag, dir): a function of (seed, env_offset + i, the env's
+        episode index, the step count) alone.  The caller's action tensors
+        are not written.  Stream-ordered: graphs captured earlier see it on
+        their next replay -- except graphs captured before this handle's first
+        set_act_noise (`noisy` still False), which hold the step kernel
+        without the noise and must be captured again."""
+        d = _lib.SatenvActNoise()
+        (d.mag[0], d.dir[0]), (d.mag[1], d.dir[1]) = ((float(x) for x in pursuer), (float(x) for x in evader))
+        d.seed, d.env_offset, d.enabled = int(seed) & (2 ** 64 - 1), int(env_offset), 1
+        self._set_noise(d)
+        self.noisy = True
+
+    def clear_act_noise(self):
+        """Back to exact execution of every action."""
+        d = self._get_noise()
+        d.enabled = 0
+        self._set_noise(d)
+
+    def act_noise(self):
+        """None while actions are executed exactly, else a dict: pursuer, evader
+        ((mag, dir) each), seed, env_offset."""
+        d = self._get_noise()
+        if not d.enabled:
+            return None
+        return {"pursuer": (d.mag[0], d.dir[0]), "evader": (d.mag[1], d.dir[1]), "seed": int(d.seed),
+                "env_offset": int(d.env_offset)}
+
     def episode_index(self):
         """int32 [N]: how many resets each env has had (0 at construction)."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
@@ -352,8 +423,8 @@ class VecSatellites:
     def full_state(self):
         """Everything a handle carries from one step to the next, as CPU numpy
         arrays: the 15 f64 and 3 i32 planes of get_state, the running episode
-        returns, the episode indices and `stats`.  The reset distribution is
-        configuration and is not part of it."""
+        returns, the episode indices and `stats`.  The reset distribution and
+        the actuation noise are configuration and are not part of it."""
         f, i = self.get_state()
         return {"f64": f.cpu().numpy(), "i32": i.cpu().numpy(), "ep_return": self.episode_return().cpu().numpy(),
                 "episode_index": self.episode_index().cpu().numpy(), "stats": self.stats.cpu().numpy().copy()}

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import norm as _norm
-from .env import VecSatellites, _typed
+from .env import VecSatellites, _typed, act_noise_spec
 from .ppo import REC_F64, REC_I32, episode_record, episode_record_reset, policy_eval, policy_eval_scripted
 from .scripted import ScriptedLaw
 
@@ -127,7 +127,7 @@ class VecEvaluator:
     (default: the trainer's N) with the trainer's env parameters.  ``seed``
     keys the sampling agents' noise (default args.seed ^ EVAL_SEED_XOR) and,
     where the trainer's env draws randomised starts, the evaluator's draws
-    from the same box."""
+    from the same box; likewise the actuation noise (evaluate(act_noise=...))."""
 
     MAX_GRAPHS = 16
 
@@ -230,8 +230,16 @@ class VecEvaluator:
         return self._graphs[key]
 
     # -- one evaluation -------------------------------------------------------------------
-    def evaluate(self, deterministic="learner", max_steps=None, states=None, seed=None, record=False, opponent=None):
+    def evaluate(self, deterministic="learner", max_steps=None, states=None, seed=None, record=False, opponent=None,
+                 act_noise="inherit"):
         tr = self.trainer
+        if isinstance(act_noise, str):
+            if act_noise != "inherit":
+                raise ValueError(f"act_noise is 'inherit', None or a spec (args_param act_noise), got {act_noise!r}")
+            now = tr.env.act_noise()             # the trainer's half-widths as they are now
+            noise = None if now is None else (now["pursuer"], now["evader"])
+        else:
+            noise = act_noise_spec(act_noise)
         flag = int(tr.flag)
         det_mask = det_mask_of(deterministic, flag)
         seed = self.seed if seed is None else int(seed)
@@ -259,6 +267,14 @@ class VecEvaluator:
                 env.clear_reset_dist()
             else:
                 env.set_reset_dist(box["lo"], box["hi"], seed, env_offset=tr.env_offset)
+            # the actuation noise under the evaluation seed too: the same errors on every call
+            if noise is None:
+                env.clear_act_noise()
+            else:
+                if not env.noisy:                # this handle's first noise: its graphs hold the step kernel without it
+                    self._graphs.clear()
+                    self._laws.clear()
+                env.set_act_noise(noise[0], noise[1], seed, env_offset=tr.env_offset)
             env.set_episode_index(None)
             if states is None:
                 env.set_state(*self._state0)

@@ -43,7 +43,7 @@ from . import norm as _norm
 from . import pool as _pool
 from . import scripted as _scripted
 from .buffer import ReplayBuffer, RolloutBuffer
-from .env import VecSatellites
+from .env import VecSatellites, act_noise_spec
 from .ppo import (PPO_continuous, PPOLearner, gae, gaussian_sample, moments, policy_act, policy_act_league,
                   policy_act_pool, policy_act_scripted, policy_value, reduce_diagnostics_sums)
 
@@ -63,7 +63,7 @@ class args_param:  # noqa: N801
                  diagnostics=False, diagnostics_rows=None, target_kl=None, reset_spread=None, reset_seed=None,
                  opponent_pool=0, opponent_latest_prob=0.5, opponent_snapshot_every=None, opponent_seed=None,
                  scripted_opponent=None, league_laws=None, league_law_prob=0.25, opponent_weighting="uniform",
-                 pfsp_power=2):
+                 pfsp_power=2, act_noise=None, act_noise_seed=None):
         self.max_train_steps = max_train_steps
         self.evaluate_freq = evaluate_freq
         self.save_freq = save_freq
@@ -151,6 +151,17 @@ class args_param:  # noqa: N801
         # (reset_seed, global env id, the env's episode index); reset_seed None = seed
         self.reset_spread = reset_spread
         self.reset_seed = reset_seed
+        # actuation noise of the vectorised engine (include/satenv.h satenv_act_noise,
+        # DESIGN.md 3.1.2): None = every commanded action is executed exactly; (mag, dir)
+        # for both agents, or {"pursuer": (mag, dir), "evader": (mag, dir)} with either key
+        # optional.  The env then executes each clipped action with a relative thrust
+        # magnitude error in +-mag (mag <= 1) and a pointing error in +-dir * |a| per
+        # component, keyed by (act_noise_seed, agent, global env id, the env's episode
+        # index, the step count); act_noise_seed None = seed.  The buffer keeps the
+        # commanded actions and their log-probs: the error is part of the environment
+        act_noise_spec(act_noise)                                        # (raises on a malformed spec)
+        self.act_noise = act_noise
+        self.act_noise_seed = act_noise_seed
         # opponent pool of the vectorised engine's self-play (satrl/pool.py): per agent
         # a ring of opponent_pool stored parameter sets (0: off, nothing is allocated
         # and the rollout makes the calls it makes without it).  In every iteration
@@ -445,6 +456,9 @@ class VecTrainer:
         rs = getattr(args, "reset_seed", None)
         self.reset_seed = self.seed if rs is None else int(rs)
         self.set_reset_spread(getattr(args, "reset_spread", None))
+        ans = getattr(args, "act_noise_seed", None)
+        self.act_noise_seed = self.seed if ans is None else int(ans)
+        self.set_act_noise(getattr(args, "act_noise", None))
         self._reset_obs()
         if self.obs_norm and int(getattr(args, "obs_norm_calib_steps", 64)) > 0:
             self._calibrate_obs_norm(int(args.obs_norm_calib_steps))
@@ -714,6 +728,26 @@ class VecTrainer:
         drew = self.env.draws
         self.env.set_reset_dist(box[0], box[1], self.reset_seed, env_offset=self.env_offset)
         if not drew:
+            self._graphs.clear()
+
+    def set_act_noise(self, spec, seed=None):
+        """The env's actuation noise (args_param act_noise; None: every action
+        is executed exactly), keyed by `seed` (default: the current noise seed)
+        and this rank's env_offset, so data-parallel shards draw by global env
+        id.  It holds from the next step on; the captured rollout graphs are
+        replayed as they are.  (Only the first spec of a trainer built without
+        one drops them: they hold the step kernel without the noise,
+        VecSatellites.set_act_noise.)"""
+        if seed is not None:
+            self.act_noise_seed = int(seed)
+        pair = act_noise_spec(spec)
+        self.act_noise = spec
+        if pair is None:
+            self.env.clear_act_noise()
+            return
+        was = self.env.noisy
+        self.env.set_act_noise(pair[0], pair[1], self.act_noise_seed, env_offset=self.env_offset)
+        if not was:
             self._graphs.clear()
 
     def _reset_obs(self):
@@ -1107,6 +1141,9 @@ class VecTrainer:
                 d["pools"][k] = s
         if self._laws:                           # (optional: a run without laws writes what it always wrote)
             d["scripted"] = {k: law.state() for k, law in self._laws.items()}
+        pair = act_noise_spec(self.act_noise)    # (optional likewise) the draw itself needs no state: it is a
+        if pair is not None:                     # function of the env id, episode index and step count above
+            d["act_noise"] = [list(pair[0]), list(pair[1]), int(self.act_noise_seed)]
         if self.pools is not None:
             d["league"] = {"law_prob": float(self.league_law_prob), "weighting": self.opponent_weighting,
                            "power": int(self.pfsp_power),
@@ -1174,6 +1211,11 @@ class VecTrainer:
                 self.set_scripted_opponent(k, _scripted.ScriptedLaw.from_state(saved_laws[k]))
         if self.pools is not None:
             self._load_league(d.get("league"))
+        noise = d.get("act_noise")               # a state without the entry: no noise
+        if noise is None:
+            self.set_act_noise(None)
+        else:
+            self.set_act_noise({"pursuer": noise[0], "evader": noise[1]}, seed=int(noise[2]))
         if "gen" in d:
             self.gen.set_state(torch.from_numpy(np.ascontiguousarray(d["gen"], dtype=np.uint8)))
         else:
@@ -1286,7 +1328,7 @@ class VecTrainer:
 
     # -- evaluation (satrl/evaluate.py) -----------------------------------------------------
     def evaluate(self, num_envs=None, deterministic="learner", max_steps=None, states=None, seed=None, record=False,
-                 opponent=None):
+                 opponent=None, act_noise="inherit"):
         """The current policies on a fresh env handle of the evaluator's own
         (`num_envs` envs, default N, this env's parameters): every env's first
         episode, at most max_steps steps (default max_episode_steps), as an
@@ -1308,7 +1350,11 @@ class VecTrainer:
         that is not filled, ValueError without a pool).  opponent="scripted":
         the frozen agent acts with its scripted law (ValueError if it has
         none); opponent=<ScriptedLaw>: with that law, on the evaluator's raw
-        observation (satrl/scripted.py).  No state of the
+        observation (satrl/scripted.py).  act_noise: "inherit" (the
+        default) runs the evaluator's env under this env's actuation noise as
+        it is now, keyed by the evaluation seed; None executes every action
+        exactly; a spec (args_param act_noise) evaluates under that spec, so
+        a sweep over it is a robustness curve.  No state of the
         trainer changes.  Under data parallelism each rank evaluates its own
         envs; results are not reduced across ranks."""
         from .evaluate import VecEvaluator
@@ -1330,7 +1376,7 @@ class VecTrainer:
         if n not in self._evaluators:
             self._evaluators[n] = VecEvaluator(self, n)
         return self._evaluators[n].evaluate(deterministic=deterministic, max_steps=max_steps, states=states, seed=seed,
-                                            record=record, opponent=opponent)
+                                            record=record, opponent=opponent, act_noise=act_noise)
 
     def evaluate_pool(self, **kw):
         """evaluate(opponent=k, **kw) against every filled slot of the frozen
