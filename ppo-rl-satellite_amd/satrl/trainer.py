@@ -751,7 +751,12 @@ class VecTrainer:
             self._graphs.clear()
 
     def _reset_obs(self):
-        """Every env restarts; buf.obs[0] is the (normalised) reset observation."""
+        """Every env restarts; buf.obs[0] is the (normalised) reset observation.
+        ellipse_params is zeroed: the surrogate has not run on the reset state
+        (it runs after every env step), and the rows of the states before the
+        restart describe no env any more."""
+        if self.ellipse_params is not None:
+            self.ellipse_params.zero_()
         if not self.obs_norm:
             self.env.reset(self.flag, obs_out=self.buf.obs[0])
             return

@@ -185,3 +185,112 @@ def test_load_state_dict_drops_the_trained_scalers():
     assert s.scalers is None
     s.load_state_dict(sd, scalers=sc)
     assert s.scalers is not None and all(np.array_equal(a, b) for a, b in zip(s.scalers, sc))
+
+
+# ---------------------------------------------------------------------------
+# the env path at ragged env counts, the grid-stride trip, and configs[4]
+# integrated: the surrogate inside VecTrainer's rollout step
+# ---------------------------------------------------------------------------
+def _oracle_feats(oracle, env):
+    """[a, e, i, f, fuel_c] f32 [n, 5] of the env's pursuers from the oracle's
+    orbital elements of env.get_state() (real_time_data_process.py:112-117)."""
+    f, _ = env.get_state()
+    f = f.cpu().numpy()
+    n = f.shape[1]
+    R_cw = np.array([27098000.0, 32306000.0, 0.0])
+    V_cw = np.array([-2350.0, 1970.0, 0.0])
+    feats = np.zeros((n, 5), dtype=np.float32)
+    for k in range(n):
+        rc, el = oracle.orbital_elements(R_cw + f[0:3, k], V_cw + f[3:6, k])
+        assert rc == 0
+        feats[k] = [el[0], el[1], el[2], el[5], f[12, k]]
+    return feats
+
+
+def _env_path_error(S, sur, oracle, env, out):
+    """`out` vs the bf16 emulation on the oracle's elements, in units of each output's scale."""
+    ref = _scaled_bf16_reference(S, sur, torch.tensor(_oracle_feats(oracle, env), device="cuda:0"))
+    osc = torch.tensor(sur.scalers[3], device="cuda:0")
+    return ((out - ref).double().abs() / osc).max().item()
+
+
+@pytest.mark.parametrize("n", [1, 17, 70])
+def test_trained_improvednn_env_path_ragged(S, oracle, n):
+    """satenv_surrogate at env counts that are no multiple of its 16-env
+    tiles or 64-env workgroups (one env; one tile and one env; one workgroup
+    and six envs): the state planes are read at plane * n + env, every env's
+    row is written and nothing past row n - 1, at test_trained_improvednn_env_path's bar."""
+    from satrl.env import VecSatellites
+    env = VecSatellites(n, device="cuda:0", d_capture=15000.0, max_episode_steps=1000)
+    env.reset(0)
+    g = torch.Generator(device="cuda:0").manual_seed(40 + n)
+    for _ in range(5):
+        env.step_autoreset(torch.rand((n, 3), device="cuda:0", generator=g) * 3.2 - 1.6,
+                           torch.rand((n, 3), device="cuda:0", generator=g) * 3.2 - 1.6)
+    sur = S.Surrogate(device="cuda:0", state_dict="trained")
+    full = torch.full((n + 1, 10), float("nan"), device="cuda:0")
+    out = sur.env_forward(env, out=full[:n])
+    torch.cuda.synchronize()
+    assert out.data_ptr() == full.data_ptr()
+    assert torch.isnan(full[n]).all()
+    assert torch.isfinite(full[:n]).all()
+    assert _env_path_error(S, sur, oracle, env, full[:n]) < 1e-2
+
+
+def test_mlp_grid_stride_second_trip(S):
+    """65 536 + 17 rows: 1024 workgroups x 64 rows cover 65 536, so the last
+    17 rows are the second trip of workgroup 0's grid-stride loop.  They equal
+    a launch of those 17 rows alone bit for bit, and the whole output meets
+    test_mlp_bf16_vs_torch's bars."""
+    n, tail = 65536 + 17, 17
+    sur = S.Surrogate(device="cuda:0", seed=1)
+    x = torch.tensor(_feats(np.random.default_rng(5), n), device="cuda:0")
+    full = torch.full((n + 1, 10), float("nan"), device="cuda:0")
+    got = sur.forward(x, out=full[:n])
+    alone = sur.forward(x[n - tail:].contiguous())
+    torch.cuda.synchronize()
+    assert torch.isnan(full[n]).all()
+    assert torch.equal(got[n - tail:].view(torch.int32), alone.view(torch.int32))
+    _close(got, S.bf16_reference(sur.net, x), 1e-2)
+    with torch.no_grad():
+        _close(got, sur.net(x), 5e-2)
+
+
+def _surrogate_trainer(use_graphs):
+    from satrl.trainer import VecTrainer, args_param
+    args = args_param(chkpt_dir="/tmp", surrogate="trained", num_envs=70, horizon=3, rollout_graph_chunk=2,
+                      hidden_width=64)
+    return VecTrainer(args, flag=0, d_capture=15000.0, use_graphs=use_graphs)
+
+
+def test_trainer_surrogate_in_the_rollout(S, oracle):
+    """configs[4] integrated: VecTrainer(surrogate="trained") evaluates the
+    net after every env step, inside the captured rollout graphs too (chunks
+    of 2 over a horizon of 3; 70 envs).  After collect() ellipse_params is
+    that of the final env state -- bitwise the same from the graphs and
+    eagerly, bitwise env_forward on that state, and at the env path's bar
+    against the emulation on the oracle's elements; set_flag restarts every
+    env and zeroes it; the next collect() rewrites every row."""
+    trs = [_surrogate_trainer(True), _surrogate_trainer(False)]
+    for tr in trs:
+        assert tr.ellipse_params.shape == (70, 10) and not tr.ellipse_params.any()
+        tr.collect()
+    torch.cuda.synchronize()
+    g, e = trs
+    assert torch.isfinite(g.ellipse_params).all()
+    assert torch.equal(g.ellipse_params.view(torch.int32), e.ellipse_params.view(torch.int32))
+    for tr in trs:
+        now = tr.surrogate.env_forward(tr.env)
+        assert torch.equal(tr.ellipse_params.view(torch.int32), now.view(torch.int32))
+        assert _env_path_error(S, tr.surrogate, oracle, tr.env, tr.ellipse_params) < 1e-2
+    for tr in trs:
+        tr.set_flag(1)
+        assert not tr.ellipse_params.any()
+        tr.ellipse_params.fill_(float("nan"))                  # whatever stays unwritten shows
+        tr.collect()
+    torch.cuda.synchronize()
+    assert torch.isfinite(g.ellipse_params).all()
+    assert torch.equal(g.ellipse_params.view(torch.int32), e.ellipse_params.view(torch.int32))
+    for tr in trs:
+        assert torch.equal(tr.ellipse_params.view(torch.int32), tr.surrogate.env_forward(tr.env).view(torch.int32))
+        assert tr.env.check_errors() == 0
