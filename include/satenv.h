@@ -238,6 +238,68 @@ int satenv_cpu_get_act_noise(const struct satenv_cpu_env* h, satenv_act_noise* h
 int satenv_cpu_act_noise_host(const satenv_act_noise* host, int64_t gid, int32_t ep, int32_t cnt, int32_t agent,
                               const float a_in[3], float a_out[3]);
 
+/* Observation noise: tracking errors (no reference counterpart: the reference
+ * observes the exact relative state, and that stays the default).  A handle
+ * carries, per TRACKED craft g (0 pursuer, 1 evader), the half-widths of two
+ * bounded errors on that craft's position (metres) and velocity (m/s)
+ * scalars: a bias held for a whole episode (bias_pos[g], bias_vel[g]) and an
+ * error redrawn every `hold` steps, the track refresh (pos[g], vel[g]).
+ * While the noise is enabled, every f32 observation row the env writes --
+ * satenv_step, satenv_step_autoreset, satenv_reset -- is the row of the
+ * MEASURED kinematics m of the true k = Pp Pv Ep Ev (init_kin order):
+ *   m[s] = k[s] + (B * z(wb[s]) + W * z(ww[s])),       s = 0 .. 11      (f64)
+ *   z(w) = 2 * ((w + 0.5) * 2^-32) - 1 in (-1, 1)
+ *   B = bias_vel[g] if s % 6 >= 3 else bias_pos[g], W likewise from vel / pos,
+ *   g = s / 6; where only one of B, W is non-zero m[s] = k[s] + that product,
+ *   where both are zero m[s] = k[s] bit for bit (-0.0 stays -0.0)
+ *   wb[4j + q] = word q of the Philox4x32-10 block with counter (lo32(gid),
+ *   hi32(gid), ep, j), key (seed, stream 5);  ww[4j + q] = word q of the block
+ *   with counter (lo32(gid), hi32(gid), ep, cnt / hold), key (seed, stream
+ *   6 + j);  j = 0, 1, 2, gid = env_offset + i, integer division
+ * every product and sum rounded once in the written order, and the row is
+ * [m_p - m_e, m_p, m_e] (differences in f64, then the cast to f32): one shared
+ * tracking picture, which both agents read and which is self-consistent, so
+ * no subtraction of columns undoes it.  (ep, cnt) of a write: after a step,
+ * the env's episode index after that launch and the step count the step used;
+ * after an in-kernel autoreset and for an env that satenv_reset resets, the
+ * advanced index and 0; for an env whose row satenv_reset only rewrites, its
+ * current index and step counter.  So a row is a function of (seed, gid, ep,
+ * cnt, truth) alone, and no state is added to get/set_state.  Truth drives
+ * everything else: obs64_out, the state planes, reward, done, the capture and
+ * range tests, the danger-zone count, fuel, dis and stats_out are what they are
+ * without the noise, bit for bit.  A craft whose four half-widths are 0 draws
+ * nothing.  Bounded uniforms for the reason given at satenv_act_noise.
+ * satenv_set_obs_noise copies *host into the handle's device block with a
+ * stream-ordered kernel; the kernels that can measure are instantiations of
+ * their own, the first enabling call switches the handle to them for good
+ * (they read `enabled` from the block), so only a graph captured BEFORE a
+ * handle's first enabling call has to be captured again.
+ * satenv_obs_noise_host is the model alone, on host pointers: k_out = m of
+ * k_in for global env id gid -- host->env_offset is not added -- and, where
+ * obs_out is not null, the f32 row of k_out; k_out = k_in where host->enabled
+ * is 0.
+ * Null pointers, non-finite or negative half-widths and hold < 1 return
+ * SATENV_ERR_ARG, with "<entry point>: <field> ..." in the error slot.       */
+typedef struct satenv_obs_noise {
+    double   bias_pos[2], bias_vel[2]; /* per tracked craft: half-width of the error held for an episode */
+    double   pos[2], vel[2];           /* ... of the error redrawn every `hold` steps */
+    uint64_t seed;
+    int64_t  env_offset;               /* global env id of env 0 (data-parallel shards) */
+    int32_t  hold;                     /* >= 1: steps a redrawn error is held (track refresh interval) */
+    int32_t  enabled;                  /* 0: observations are exact */
+} satenv_obs_noise;
+int satenv_default_obs_noise(satenv_obs_noise* host);   /* zeros, hold 1, enabled 0 */
+int satenv_set_obs_noise(satenv_env* h, const satenv_obs_noise* host, void* stream);
+int satenv_get_obs_noise(const satenv_env* h, satenv_obs_noise* host);
+int satenv_obs_noise_host(const satenv_obs_noise* host, int64_t gid, int32_t ep, int32_t cnt,
+                          const double k_in[12], double k_out[12], float obs_out[18]);
+/* ... and on the host build's handle (host pointers, synchronous) */
+int satenv_cpu_default_obs_noise(satenv_obs_noise* host);
+int satenv_cpu_set_obs_noise(struct satenv_cpu_env* h, const satenv_obs_noise* host, void* stream);
+int satenv_cpu_get_obs_noise(const struct satenv_cpu_env* h, satenv_obs_noise* host);
+int satenv_cpu_obs_noise_host(const satenv_obs_noise* host, int64_t gid, int32_t ep, int32_t cnt,
+                              const double k_in[12], double k_out[12], float obs_out[18]);
+
 /* Time_window_of_danger_zone(R0_c, V0_c, R0_t, V0_t, Delta_V_c=fuel)
  *   .calculate_number_of_hanger_area()   satellite_function.py:18-99,341-373
  * on n independent absolute states: states f64 [n][12] = R_c V_c R_t V_t,

@@ -10,7 +10,7 @@
  * synchronous).  It is what the drop-in runs with device="cpu" (BASELINE
  * configs[0]: CPPO_main on CPU, no GPU) and the CPU baseline of bench.py.
  * The entry points without a reference counterpart (reset distribution,
- * episode index and return, actuation noise) are declared in satenv.h, beside
+ * episode index and return, actuation and observation noise) are declared in satenv.h, beside
  * the structs and contracts they share with the device build.
  * Replaces, like satenv.h: satellites.__init__ / reset / step
  * (environment.py:26-255), the CPPO_main.py:119-153 loop around them, and

@@ -48,6 +48,8 @@ struct satenv_cpu_env {
   satenv_reset_dist dist{};         // ... and as satenv_cpu_set_reset_dist was given it
   ActNoise an{};                    // the actuation noise as the step reads it
   satenv_act_noise noise{};         // ... and as satenv_cpu_set_act_noise was given it
+  ObsNoise on{};                    // the observation noise as the step and the reset read it
+  satenv_obs_noise obsn{};          // ... and as satenv_cpu_set_obs_noise was given it
 };
 
 namespace {
@@ -55,7 +57,7 @@ namespace {
 // step_lane for env i; st (may be null) = the four per-env stat planes [4][n]
 void step_env(satenv_cpu_env* h, const StepIO& io, int64_t i, bool autoreset, double* st) {
   StepStats s;
-  const int rc = step_lane<true, true, true>(h->prm, h->n, h->f64.data(), h->i32.data(), io, i, autoreset, s);
+  const int rc = step_lane<true, true, true, true>(h->prm, h->n, h->f64.data(), h->i32.data(), io, i, autoreset, s);
   if (rc) {
 #pragma omp critical(satenv_cpu_err)
     if (h->err == 0) h->err = rc;
@@ -86,6 +88,8 @@ int satenv_cpu_create(satenv_cpu_env** out, int64_t num_envs, const satenv_param
   h->i32.assign((size_t)kI32Planes * num_envs, 0);
   satenv_cpu_default_reset_dist(&h->dist);
   reset_dist_pack(h->dist, h->rd);
+  satenv_cpu_default_obs_noise(&h->obsn);
+  obs_noise_pack(h->obsn, h->on);
   for (int64_t i = 0; i < num_envs; ++i) init_env(h->prm, num_envs, h->f64.data(), h->i32.data(), i);
   *out = h;
   return SATENV_OK;
@@ -118,7 +122,8 @@ int satenv_cpu_reset(satenv_cpu_env* h, int32_t flag, const uint8_t* env_mask, f
   h->prm.flag = flag;
 #pragma omp parallel for num_threads(h->threads) schedule(static)
   for (int64_t i = 0; i < h->n; ++i)
-    reset_env(h->prm, &h->rd, h->n, h->f64.data(), h->i32.data(), flag, env_mask, obs_out, obs64_out, i);
+    reset_env<true>(h->prm, &h->rd, h->n, h->f64.data(), h->i32.data(), flag, env_mask, obs_out, obs64_out, i,
+                    &h->on);
   return SATENV_OK;
 }
 
@@ -126,7 +131,7 @@ int satenv_cpu_step(satenv_cpu_env* h, const float* pa, const float* ea, const i
                     float* obs_out, double* obs64_out, double* reward_out, uint8_t* done_out, void* /*stream*/) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_cpu_step: null argument");
   const StepIO io{pa, ea, episode_count, obs_out, obs64_out, reward_out, nullptr, done_out, nullptr, nullptr, &h->rd,
-                  &h->an};
+                  &h->an, &h->on};
 #pragma omp parallel for num_threads(h->threads) schedule(dynamic, 64)
   for (int64_t i = 0; i < h->n; ++i) step_env(h, io, i, false, nullptr);
   return SATENV_OK;
@@ -136,7 +141,7 @@ int satenv_cpu_step_autoreset(satenv_cpu_env* h, const float* pa, const float* e
                               float* reward_out, uint8_t* done_out, double* stats_out, void* /*stream*/) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_cpu_step_autoreset: null argument");
   const StepIO io{pa, ea, nullptr, obs_out, nullptr, nullptr, reward_out, done_out, nullptr, nullptr, &h->rd,
-                  &h->an};
+                  &h->an, &h->on};
   const int64_t n = h->n;
   std::vector<double> st;
   if (stats_out) st.assign((size_t)4 * n, 0.0);
@@ -223,6 +228,37 @@ int satenv_cpu_act_noise_host(const satenv_act_noise* d, int64_t gid, int32_t ep
                               const float a_in[3], float a_out[3]) {
   if (const char* bad = act_noise_host(d, gid, ep, cnt, agent, a_in, a_out))
     return fail(SATENV_ERR_ARG, std::string("satenv_cpu_act_noise_host: ") + bad);
+  return SATENV_OK;
+}
+
+int satenv_cpu_default_obs_noise(satenv_obs_noise* d) {
+  if (!d) return fail(SATENV_ERR_ARG, "satenv_cpu_default_obs_noise: null");
+  std::memset(d, 0, sizeof(*d));
+  d->hold = 1;
+  return SATENV_OK;
+}
+
+int satenv_cpu_set_obs_noise(satenv_cpu_env* h, const satenv_obs_noise* d, void* /*stream*/) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_cpu_set_obs_noise: null argument");
+  ObsNoise on;
+  if (const char* bad = obs_noise_pack(*d, on))
+    return fail(SATENV_ERR_ARG, std::string("satenv_cpu_set_obs_noise: ") + bad);
+  h->on = on;
+  h->obsn = *d;
+  h->obsn.enabled = d->enabled != 0;
+  return SATENV_OK;
+}
+
+int satenv_cpu_get_obs_noise(const satenv_cpu_env* h, satenv_obs_noise* d) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_cpu_get_obs_noise: null argument");
+  *d = h->obsn;
+  return SATENV_OK;
+}
+
+int satenv_cpu_obs_noise_host(const satenv_obs_noise* d, int64_t gid, int32_t ep, int32_t cnt,
+                              const double k_in[12], double k_out[12], float obs_out[18]) {
+  if (const char* bad = obs_noise_host(d, gid, ep, cnt, k_in, k_out, obs_out))
+    return fail(SATENV_ERR_ARG, std::string("satenv_cpu_obs_noise_host: ") + bad);
   return SATENV_OK;
 }
 

@@ -75,14 +75,16 @@ __device__ __forceinline__ void wave_stats(double* stats, StepStats s) {
 // the default instantiations, which handles that never enabled one launch, do not carry that code.
 // NOISE: step_begin perturbs the clipped actions by the handle's actuation noise (satenv_step.h
 // act_noise); instantiated with DRAW only, for the handles that enabled it once.
+// MEAS: step_end writes the f32 row of the measured kinematics (satenv_step.h obs_measure);
+// instantiated with DRAW and NOISE only, the last rung of the same ladder.
 // One lane per env, the count's four solves one after another (64-lane blocks):
-template <bool AUTORESET, bool RK45 = false, bool DRAW = false, bool NOISE = false>
+template <bool AUTORESET, bool RK45 = false, bool DRAW = false, bool NOISE = false, bool MEAS = false>
 __global__ void __launch_bounds__(64) step_kernel(const Params prm, int64_t n, double* __restrict__ f64,
                                                   int32_t* __restrict__ i32, StepIO io, unsigned long long*) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   StepStats s;
   if (i < n) {
-    const int rc = step_lane<RK45, DRAW, NOISE>(prm, n, f64, i32, io, i, AUTORESET, s);
+    const int rc = step_lane<RK45, DRAW, NOISE, MEAS>(prm, n, f64, i32, io, i, AUTORESET, s);
     if (rc) atomicCAS(io.err, 0, rc);
   }
   if (io.stats) wave_stats(io.stats, s);
@@ -110,7 +112,7 @@ __device__ __forceinline__ bool lane_head(const Params& prm, int64_t n, const do
 // latency bound: 16384 envs are only 256 waves).  Bit-identical to
 // step_kernel: every problem runs the same hybrd1.
 constexpr int kSplitEnvs = 64;
-template <bool AUTORESET, bool RK45 = false, bool DRAW = false, bool NOISE = false>
+template <bool AUTORESET, bool RK45 = false, bool DRAW = false, bool NOISE = false, bool MEAS = false>
 __global__ void __launch_bounds__(256) step_kernel_split(const Params prm, int64_t n, double* __restrict__ f64,
                                                          int32_t* __restrict__ i32, StepIO io, unsigned long long*) {
   __shared__ double sA[4][kSplitEnvs], sSt[4][kSplitEnvs], sDvm[4][kSplitEnvs], sX[4][kSplitEnvs];
@@ -158,7 +160,7 @@ __global__ void __launch_bounds__(256) step_kernel_split(const Params prm, int64
       }
       step_reward(prm, L, cnt);
     }
-    step_end<DRAW>(prm, n, f64, i32, io, i, AUTORESET, L, s);
+    step_end<DRAW, MEAS>(prm, n, f64, i32, io, i, AUTORESET, L, s);
   }
   if (w == 0 && io.stats) wave_stats(io.stats, s);
 }
@@ -252,7 +254,7 @@ __device__ __forceinline__ RfSolve get_rf_problem(const WideSmem<E>& sm, int w, 
 // ENVS envs per workgroup (lanes >= ENVS of each wave idle): fewer envs per
 // wave put more waves, i.e. more independent dependency chains, on each SIMD
 // when N is small (the step is latency bound there); 64 at large N
-template <bool AUTORESET, int ENVS, bool SPAN = false, bool DRAW = false, bool NOISE = false>
+template <bool AUTORESET, int ENVS, bool SPAN = false, bool DRAW = false, bool NOISE = false, bool MEAS = false>
 __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_t n, double* __restrict__ f64,
                                                         int32_t* __restrict__ i32, StepIO io,
                                                         unsigned long long* __restrict__ span) {
@@ -359,7 +361,7 @@ __global__ void __launch_bounds__(256) step_kernel_wide(const Params prm, int64_
       for (int c = 0; c < 4; ++c) t[c] = sm.rt[c][lane];
       step_reward_terms(prm, L, cnt, t);
     }
-    step_end<DRAW>(prm, n, f64, i32, io, i, AUTORESET, L, s);
+    step_end<DRAW, MEAS>(prm, n, f64, i32, io, i, AUTORESET, L, s);
   }
   if (w == 0 && io.stats) wave_stats(io.stats, s);
   ENV_PROBE(6);
@@ -372,12 +374,23 @@ __global__ void __launch_bounds__(256) reset_kernel(const Params prm, const Rese
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) reset_env(prm, rd, n, f64, i32, flag, mask, obs, obs64, i);
 }
+// ... of the handles that enabled observation noise once: the f32 rows are measured
+__global__ void __launch_bounds__(256) reset_kernel_meas(const Params prm, const ResetDist* __restrict__ rd,
+                                                         const ObsNoise* __restrict__ on, int64_t n,
+                                                         double* __restrict__ f64, int32_t* __restrict__ i32,
+                                                         int32_t flag, const uint8_t* mask, float* obs,
+                                                         double* obs64) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) reset_env<true>(prm, rd, n, f64, i32, flag, mask, obs, obs64, i, on);
+}
 
 // satenv_set_reset_dist: the struct rides in the argument segment, one lane
 // writes it into the handle's block -- stream-ordered with the steps around it
 __global__ void set_reset_dist_kernel(const ResetDist d, ResetDist* __restrict__ dst) { *dst = d; }
 // satenv_set_act_noise: the same for the handle's actuation-noise block
 __global__ void set_act_noise_kernel(const ActNoise d, ActNoise* __restrict__ dst) { *dst = d; }
+// satenv_set_obs_noise: ... and for its observation-noise block
+__global__ void set_obs_noise_kernel(const ObsNoise d, ObsNoise* __restrict__ dst) { *dst = d; }
 
 __global__ void init_kernel(const Params prm, int64_t n, double* f64, int32_t* i32) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -683,6 +696,9 @@ struct satenv_env {
   ActNoise* an = nullptr;           // the actuation noise as the kernels read it (device)
   satenv_act_noise noise{};         // ... and as satenv_set_act_noise was given it
   bool noisy = false;               // noise was enabled once: launch the DRAW + NOISE step kernels
+  ObsNoise* on = nullptr;           // the observation noise as the kernels read it (device)
+  satenv_obs_noise obsn{};          // ... and as satenv_set_obs_noise was given it
+  bool meas = false;                // it was enabled once: launch the DRAW + NOISE + MEAS kernels
   int kind = 2;    // step_kernel_wide (2), step_kernel_split (1) or the one-lane step_kernel (0)
   int wide_envs = 64;   // envs per workgroup of the wide kernel (16 / 32 for A/B; fewer envs per
                         // workgroup measured no faster)
@@ -692,24 +708,24 @@ namespace {
 
 int grid_for(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
-template <bool AR, bool DRAW, bool NOISE>
+template <bool AR, bool DRAW, bool NOISE, bool MEAS>
 void launch_step_draw(satenv_env* h, const StepIO& io, void* stream) {
   void (*plain)(const Params, int64_t, double*, int32_t*, StepIO, unsigned long long*) =
-      step_kernel<AR, false, DRAW, NOISE>;
+      step_kernel<AR, false, DRAW, NOISE, MEAS>;
   decltype(plain) probed = nullptr;
   int envs = 64, threads = 256;   // per workgroup
   if (h->prm.propagator == 2) {   // the RK45 instantiation (its registers stay out of the STM kernels)
-    plain = step_kernel_split<AR, true, DRAW, NOISE>;
+    plain = step_kernel_split<AR, true, DRAW, NOISE, MEAS>;
   } else if (h->kind == 2) {
     envs = h->wide_envs;
-    plain = envs == 16   ? step_kernel_wide<AR, 16, false, DRAW, NOISE>
-            : envs == 32 ? step_kernel_wide<AR, 32, false, DRAW, NOISE>
-                         : step_kernel_wide<AR, 64, false, DRAW, NOISE>;
+    plain = envs == 16   ? step_kernel_wide<AR, 16, false, DRAW, NOISE, MEAS>
+            : envs == 32 ? step_kernel_wide<AR, 32, false, DRAW, NOISE, MEAS>
+                         : step_kernel_wide<AR, 64, false, DRAW, NOISE, MEAS>;
     // the product geometry (64 envs per workgroup) has a SPAN instantiation
     // for the bench's live launch spans (span_probe.h)
-    if (envs == 64) probed = step_kernel_wide<AR, 64, true, DRAW, NOISE>;
+    if (envs == 64) probed = step_kernel_wide<AR, 64, true, DRAW, NOISE, MEAS>;
   } else if (h->kind == 1) {
-    plain = step_kernel_split<AR, false, DRAW, NOISE>;
+    plain = step_kernel_split<AR, false, DRAW, NOISE, MEAS>;
   } else {
     threads = 64;
   }
@@ -719,12 +735,14 @@ void launch_step_draw(satenv_env* h, const StepIO& io, void* stream) {
 }
 
 // only an autoreset step resets, so only it has DRAW instantiations of its own; the NOISE
-// ones are <DRAW, NOISE> for both (a step without autoreset never reaches the draw)
+// ones are <DRAW, NOISE> for both (a step without autoreset never reaches the draw), and the
+// MEAS ones <DRAW, NOISE, MEAS>: one more rung, not a second ladder
 template <bool AR>
 void launch_step(satenv_env* h, const StepIO& io, void* stream) {
-  if (h->noisy) launch_step_draw<AR, true, true>(h, io, stream);
-  else if (AR && h->draw) launch_step_draw<AR, AR, false>(h, io, stream);
-  else launch_step_draw<AR, false, false>(h, io, stream);
+  if (h->meas) launch_step_draw<AR, true, true, true>(h, io, stream);
+  else if (h->noisy) launch_step_draw<AR, true, true, false>(h, io, stream);
+  else if (AR && h->draw) launch_step_draw<AR, AR, false, false>(h, io, stream);
+  else launch_step_draw<AR, false, false, false>(h, io, stream);
 }
 
 }  // namespace
@@ -810,6 +828,11 @@ int satenv_create(satenv_env** out, int64_t num_envs, const satenv_params* p, in
   act_noise_pack(h->noise, an);
   if (e == hipSuccess) e = hipMalloc(&h->an, sizeof(ActNoise));
   if (e == hipSuccess) e = hipMemcpy(h->an, &an, sizeof(ActNoise), hipMemcpyHostToDevice);
+  ObsNoise on{};
+  satenv_default_obs_noise(&h->obsn);
+  obs_noise_pack(h->obsn, on);
+  if (e == hipSuccess) e = hipMalloc(&h->on, sizeof(ObsNoise));
+  if (e == hipSuccess) e = hipMemcpy(h->on, &on, sizeof(ObsNoise), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     satenv_destroy(h);
     return fail(SATENV_ERR_HIP, std::string("satenv_create: ") + hipGetErrorString(e));
@@ -833,6 +856,7 @@ int satenv_destroy(satenv_env* h) {
   if (h->err) (void)hipFree(h->err);
   if (h->rd) (void)hipFree(h->rd);
   if (h->an) (void)hipFree(h->an);
+  if (h->on) (void)hipFree(h->on);
   delete h;
   return SATENV_OK;
 }
@@ -855,8 +879,12 @@ int satenv_reset(satenv_env* h, int32_t flag, const uint8_t* env_mask, float* ob
   if (!h) return fail(SATENV_ERR_ARG, "satenv_reset: null handle");
   if (flag < 0 || flag > 2) return fail(SATENV_ERR_ARG, "satenv_reset: Flag must be 0, 1 or 2");
   h->prm.flag = flag;
-  hipLaunchKernelGGL(reset_kernel, dim3(grid_for(h->n, 256)), dim3(256), 0, (hipStream_t)stream, h->prm, h->rd,
-                     h->n, h->f64, h->i32, flag, env_mask, obs_out, obs64_out);
+  if (h->meas)
+    hipLaunchKernelGGL(reset_kernel_meas, dim3(grid_for(h->n, 256)), dim3(256), 0, (hipStream_t)stream, h->prm,
+                       h->rd, h->on, h->n, h->f64, h->i32, flag, env_mask, obs_out, obs64_out);
+  else
+    hipLaunchKernelGGL(reset_kernel, dim3(grid_for(h->n, 256)), dim3(256), 0, (hipStream_t)stream, h->prm, h->rd,
+                       h->n, h->f64, h->i32, flag, env_mask, obs_out, obs64_out);
   HIP_TRY(hipGetLastError());
   return SATENV_OK;
 }
@@ -865,7 +893,7 @@ int satenv_step(satenv_env* h, const float* pa, const float* ea, const int32_t* 
                 double* obs64_out, double* reward_out, uint8_t* done_out, void* stream) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_step: null argument");
   StepIO io{pa, ea, episode_count, obs_out, obs64_out, reward_out, nullptr, done_out, nullptr, h->err, h->rd,
-            h->an};
+            h->an, h->on};
   launch_step<false>(h, io, stream);
   HIP_TRY(hipGetLastError());
   return SATENV_OK;
@@ -875,7 +903,7 @@ int satenv_step_autoreset(satenv_env* h, const float* pa, const float* ea, float
                           uint8_t* done_out, double* stats_out, void* stream) {
   if (!h || !pa || !ea) return fail(SATENV_ERR_ARG, "satenv_step_autoreset: null argument");
   StepIO io{pa, ea, nullptr, obs_out, nullptr, nullptr, reward_out, done_out, stats_out, h->err, h->rd,
-            h->an};
+            h->an, h->on};
   launch_step<true>(h, io, stream);
   HIP_TRY(hipGetLastError());
   return SATENV_OK;
@@ -962,6 +990,39 @@ int satenv_act_noise_host(const satenv_act_noise* d, int64_t gid, int32_t ep, in
                           const float a_in[3], float a_out[3]) {
   if (const char* bad = act_noise_host(d, gid, ep, cnt, agent, a_in, a_out))
     return fail(SATENV_ERR_ARG, std::string("satenv_act_noise_host: ") + bad);
+  return SATENV_OK;
+}
+
+int satenv_default_obs_noise(satenv_obs_noise* d) {
+  if (!d) return fail(SATENV_ERR_ARG, "satenv_default_obs_noise: null");
+  std::memset(d, 0, sizeof(*d));
+  d->hold = 1;
+  return SATENV_OK;
+}
+
+int satenv_set_obs_noise(satenv_env* h, const satenv_obs_noise* d, void* stream) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_set_obs_noise: null argument");
+  ObsNoise on;
+  if (const char* bad = obs_noise_pack(*d, on))
+    return fail(SATENV_ERR_ARG, std::string("satenv_set_obs_noise: ") + bad);
+  hipLaunchKernelGGL(set_obs_noise_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, on, h->on);
+  HIP_TRY(hipGetLastError());
+  h->obsn = *d;
+  h->obsn.enabled = d->enabled != 0;
+  if (d->enabled) h->meas = true;   // from now on the MEAS kernels, whatever the block says later
+  return SATENV_OK;
+}
+
+int satenv_get_obs_noise(const satenv_env* h, satenv_obs_noise* d) {
+  if (!h || !d) return fail(SATENV_ERR_ARG, "satenv_get_obs_noise: null argument");
+  *d = h->obsn;
+  return SATENV_OK;
+}
+
+int satenv_obs_noise_host(const satenv_obs_noise* d, int64_t gid, int32_t ep, int32_t cnt, const double k_in[12],
+                          double k_out[12], float obs_out[18]) {
+  if (const char* bad = obs_noise_host(d, gid, ep, cnt, k_in, k_out, obs_out))
+    return fail(SATENV_ERR_ARG, std::string("satenv_obs_noise_host: ") + bad);
   return SATENV_OK;
 }
 

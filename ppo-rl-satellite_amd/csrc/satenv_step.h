@@ -22,6 +22,8 @@ constexpr int kPlaneRet = 15;
 constexpr int kPlaneDz = 0, kPlaneCount = 1, kPlaneBits = 2, kPlaneEp = 3;
 constexpr uint32_t kResetStream = 2;   // philox_key stream of the reset draw (0 / 1: the agents' action noise)
 constexpr uint32_t kActNoiseStream = 3;   // ... and of agent g's actuation noise: 3 + g
+constexpr uint32_t kObsBiasStream = 5;    // ... of the tracking errors' episode bias
+constexpr uint32_t kObsNoiseStream = 6;   // ... and of block j of their refreshed part: 6 + j, j = 0, 1, 2
 
 struct alignas(8) F32x2 { float x, y; };
 
@@ -89,6 +91,46 @@ inline const char* act_noise_pack(const satenv_act_noise& in, ActNoise& out) {
   return nullptr;
 }
 
+// The handle's observation noise as the kernels read it (satenv_obs_noise,
+// include/satenv.h): per tracked craft g the half-widths of
+// the episode bias and of the refreshed error on its position and velocity
+// scalars, and the keys of the four streams.  A block of its own beside the
+// ActNoise, written by its own setter launch and read where a kernel writes
+// the f32 observation row.
+struct ObsNoise {
+  double bias_pos[2], bias_vel[2], pos[2], vel[2];
+  uint32_t kb0, kb1;        // philox_key(seed, kObsBiasStream)
+  uint32_t kw0[3], kw1[3];  // philox_key(seed, kObsNoiseStream + j)
+  int64_t env_offset;       // global env id of env 0
+  int32_t hold;             // >= 1
+  int32_t enabled;
+};
+
+// satenv_obs_noise -> ObsNoise; nullptr, or what is wrong with which field
+inline const char* obs_noise_pack(const satenv_obs_noise& in, ObsNoise& out) {
+  static const char* const kBad[2][4] = {
+      {"bias_pos[0] must be finite and >= 0", "bias_vel[0] must be finite and >= 0",
+       "pos[0] must be finite and >= 0", "vel[0] must be finite and >= 0"},
+      {"bias_pos[1] must be finite and >= 0", "bias_vel[1] must be finite and >= 0",
+       "pos[1] must be finite and >= 0", "vel[1] must be finite and >= 0"}};
+  for (int g = 0; g < 2; ++g) {
+    const double v[4] = {in.bias_pos[g], in.bias_vel[g], in.pos[g], in.vel[g]};
+    for (int f = 0; f < 4; ++f)
+      if (!std::isfinite(v[f]) || !(v[f] >= 0.0)) return kBad[g][f];
+    out.bias_pos[g] = in.bias_pos[g];
+    out.bias_vel[g] = in.bias_vel[g];
+    out.pos[g] = in.pos[g];
+    out.vel[g] = in.vel[g];
+  }
+  if (in.hold < 1) return "hold must be >= 1";
+  philox_key(in.seed, kObsBiasStream, out.kb0, out.kb1);
+  for (int j = 0; j < 3; ++j) philox_key(in.seed, kObsNoiseStream + (uint32_t)j, out.kw0[j], out.kw1[j]);
+  out.env_offset = in.env_offset;
+  out.hold = in.hold;
+  out.enabled = in.enabled != 0;
+  return nullptr;
+}
+
 struct StepIO {
   const float* pa;
   const float* ea;
@@ -102,6 +144,7 @@ struct StepIO {
   int32_t* err;
   const ResetDist* rd;        // the handle's reset distribution (never null)
   const ActNoise* an;         // the handle's actuation noise (never null)
+  const ObsNoise* on;         // the handle's observation noise (never null)
 };
 
 // one env's share of a step's statistics (step_autoreset's stats_out): episode
@@ -213,6 +256,87 @@ inline const char* act_noise_host(const satenv_act_noise* in, int64_t gid, int32
   return nullptr;
 }
 
+// The measured kinematics m of the true k of global env `gid` at step `cnt` of
+// its episode `ep`: scalar s of tracked craft g = s / 6 is
+//   m[s] = k[s] + (B * z(wb[s]) + W * z(ww[s])),  z(w) = 2 * ((w + 0.5) * 2^-32) - 1
+// with B the craft's bias half-width (bias_vel for a velocity scalar, s % 6 >=
+// 3, else bias_pos), W its refreshed one (vel / pos), wb the 12 words of three
+// Philox4x32-10 blocks, counter (gid, ep, j), key (seed, stream 5), and ww
+// those of three blocks, counter (gid, ep, cnt / hold), key (seed, stream 6 +
+// j).  A zero half-width leaves its product out (so m[s] is k[s] bit for bit
+// where both are zero), and a block none of whose scalars has a non-zero
+// half-width is not drawn.  Integer rounds, an exact u, f64 products and sums
+// rounded once each: the same bits on both targets (as act_noise).  The half-
+// widths are uniform, so every branch on them is a scalar one; the six chains
+// are independent of each other and of the step, and unrolled side by side.
+SATENV_HD void obs_measure(const ObsNoise* d, uint64_t gid, uint32_t ep, uint32_t cnt, const double (&k)[12],
+                           double (&m)[12]) {
+  double B[2][2], W[2][2];   // [craft][position / velocity]
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    B[g][0] = rd_load(&d->bias_pos[g]);
+    B[g][1] = rd_load(&d->bias_vel[g]);
+    W[g][0] = rd_load(&d->pos[g]);
+    W[g][1] = rd_load(&d->vel[g]);
+  }
+  const bool has_b[2] = {B[0][0] != 0.0 || B[0][1] != 0.0, B[1][0] != 0.0 || B[1][1] != 0.0};
+  const bool has_w[2] = {W[0][0] != 0.0 || W[0][1] != 0.0, W[1][0] != 0.0 || W[1][1] != 0.0};
+  const uint32_t win = cnt / (uint32_t)rd_load(&d->hold);
+  const uint32_t g0 = (uint32_t)gid, g1 = (uint32_t)(gid >> 32);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {   // block j: scalars 4j .. 4j + 3 (craft 0 in blocks 0, 1; craft 1 in 1, 2)
+    uint32_t wb[4] = {g0, g1, ep, (uint32_t)j}, ww[4] = {g0, g1, ep, win};
+    if ((j <= 1 && has_b[0]) || (j >= 1 && has_b[1])) philox4x32_10(wb, rd_load(&d->kb0), rd_load(&d->kb1));
+    if ((j <= 1 && has_w[0]) || (j >= 1 && has_w[1])) philox4x32_10(ww, rd_load(&d->kw0[j]), rd_load(&d->kw1[j]));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int s = 4 * j + q, g = s / 6, v = (s % 6) >= 3 ? 1 : 0;
+      const double b = B[g][v], w = W[g][v];
+      const double eb = b * (2.0 * (((double)wb[q] + 0.5) * 0x1p-32) - 1.0);
+      const double ew = w * (2.0 * (((double)ww[q] + 0.5) * 0x1p-32) - 1.0);
+      if (b != 0.0 && w != 0.0) m[s] = k[s] + (eb + ew);
+      else if (b != 0.0) m[s] = k[s] + eb;
+      else if (w != 0.0) m[s] = k[s] + ew;
+      else m[s] = k[s];
+    }
+  }
+}
+
+// The f32 observation row of env i whose true kinematics are k, at (ep, cnt) of
+// the rule in include/satenv.h: write_obs of the measured kinematics while the
+// handle's observation noise is enabled, of the truth otherwise.  obs64 is the
+// truth either way.
+SATENV_HD void write_obs_measured(const ObsNoise* d, float* obs, double* obs64, int64_t i, uint32_t ep,
+                                  uint32_t cnt, const double (&k)[12]) {
+  if (obs != nullptr && rd_load(&d->enabled)) {
+    double m[12];
+    obs_measure(d, (uint64_t)rd_load(&d->env_offset) + (uint64_t)i, ep, cnt, k, m);
+    write_obs(obs, nullptr, i, m);
+    write_obs(nullptr, obs64, i, k);
+  } else {
+    write_obs(obs, obs64, i, k);
+  }
+}
+
+// satenv_obs_noise_host and its satenv_cpu_ twin: the model on host pointers;
+// nullptr, or the refusal's reason
+inline const char* obs_noise_host(const satenv_obs_noise* in, int64_t gid, int32_t ep, int32_t cnt,
+                                  const double* k_in, double* k_out, float* obs_out) {
+  if (!in || !k_in || !k_out) return "null argument";
+  ObsNoise d{};
+  if (const char* bad = obs_noise_pack(*in, d)) return bad;
+  double k[12], m[12];
+  for (int c = 0; c < 12; ++c) m[c] = k[c] = k_in[c];
+  if (d.enabled) obs_measure(&d, (uint64_t)gid, (uint32_t)ep, (uint32_t)cnt, k, m);
+  for (int c = 0; c < 12; ++c) k_out[c] = m[c];
+  if (obs_out) {
+    alignas(8) float row[18];
+    write_obs(row, nullptr, 0, m);
+    for (int c = 0; c < 18; ++c) obs_out[c] = row[c];
+  }
+  return nullptr;
+}
+
 // One reset of env i (the masked reset and the autoreset): the kinematics it
 // starts from and its vel_int bit -- the reference's int64 constants (vel_int
 // 1) or, with the distribution enabled, the draw of this episode index (float
@@ -249,8 +373,11 @@ SATENV_HD void init_env(const Params& p, int64_t n, double* f64, int32_t* i32, i
 }
 
 // reset(Flag) of env i where the mask selects it (environment.py:66-79), and its obs either way
+// kMeas: the row is measured under the handle's observation noise `on` (the
+// reset kernel of handles that enabled it once, and the host build)
+template <bool kMeas = false>
 SATENV_HD void reset_env(const Params& prm, const ResetDist* rd, int64_t n, double* f64, int32_t* i32, int32_t flag,
-                         const uint8_t* mask, float* obs, double* obs64, int64_t i) {
+                         const uint8_t* mask, float* obs, double* obs64, int64_t i, const ObsNoise* on = nullptr) {
   double k[12];
   if (mask == nullptr || mask[i] != 0) {
     const int vi = reset_state<true>(prm, rd, n, i32, i, k);
@@ -264,7 +391,10 @@ SATENV_HD void reset_env(const Params& prm, const ResetDist* rd, int64_t n, doub
 #pragma unroll
     for (int c = 0; c < 12; ++c) k[c] = f64[c * n + i];
   }
-  write_obs(obs, obs64, i, k);
+  if constexpr (kMeas)   // a reset env: its advanced index and count 0; the others: their planes as they are
+    write_obs_measured(on, obs, obs64, i, (uint32_t)i32[kPlaneEp * n + i], (uint32_t)i32[kPlaneCount * n + i], k);
+  else
+    write_obs(obs, obs64, i, k);
 }
 
 // ---------------------------------------------------------------------------
@@ -436,7 +566,9 @@ SATENV_HD void step_reward(const Params& prm, Lane& L, int cnt) {
   step_reward_terms(prm, L, cnt, t);
 }
 
-template <bool kDraw = false>
+// kMeas: the instantiation of handles that enabled observation noise once
+// (the f32 row is write_obs_measured's); the others do not carry its code.
+template <bool kDraw = false, bool kMeas = false>
 SATENV_HD void step_end(const Params& prm, int64_t n, double* __restrict__ f64,
                                          int32_t* __restrict__ i32, const StepIO& io, int64_t i, bool autoreset,
                                          Lane& L, StepStats& s) {
@@ -453,7 +585,10 @@ SATENV_HD void step_end(const Params& prm, int64_t n, double* __restrict__ f64,
     vi_out = reset_state<kDraw>(prm, io.rd, n, i32, i, L.k);
     L.count = 0;
   }
-  write_obs(io.obs, io.obs64, i, L.k);
+  if constexpr (kMeas)   // the episode index after this launch, the count this step used (0 after the autoreset)
+    write_obs_measured(io.on, io.obs, io.obs64, i, (uint32_t)i32[kPlaneEp * n + i], (uint32_t)L.count, L.k);
+  else
+    write_obs(io.obs, io.obs64, i, L.k);
 #pragma unroll
   for (int c = 0; c < 12; ++c) f64[c * n + i] = L.k[c];
   f64[12 * n + i] = L.fuel_c;
@@ -468,7 +603,7 @@ SATENV_HD void step_end(const Params& prm, int64_t n, double* __restrict__ f64,
 // The whole step of env i in one lane (the count's four solves one after
 // another): the one-lane kernel and the host build.  Returns the error code
 // to record, 0 if none; the caller owns the (first-wins) error sink.
-template <bool kRk45, bool kDraw, bool kNoise = false>
+template <bool kRk45, bool kDraw, bool kNoise = false, bool kMeas = false>
 SATENV_HD int step_lane(const Params& prm, int64_t n, double* __restrict__ f64, int32_t* __restrict__ i32,
                         const StepIO& io, int64_t i, bool autoreset, StepStats& s) {
   Lane L;
@@ -480,7 +615,7 @@ SATENV_HD int step_lane(const Params& prm, int64_t n, double* __restrict__ f64, 
     if (err == 0) err = rc;
     step_reward(prm, L, cnt);
   }
-  step_end<kDraw>(prm, n, f64, i32, io, i, autoreset, L, s);
+  step_end<kDraw, kMeas>(prm, n, f64, i32, io, i, autoreset, L, s);
   return err;
 }
 

@@ -57,6 +57,13 @@ class SatenvActNoise(C.Structure):
                 ("enabled", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SatenvObsNoise(C.Structure):
+    """Mirror of ``satenv_obs_noise`` (include/satenv.h)."""
+    _fields_ = [("bias_pos", C.c_double * 2), ("bias_vel", C.c_double * 2), ("pos", C.c_double * 2),
+                ("vel", C.c_double * 2), ("seed", C.c_uint64), ("env_offset", C.c_int64), ("hold", C.c_int32),
+                ("enabled", C.c_int32)]
+
+
 class StepPlan(C.Structure):
     """Mirror of ``satrl_ppo_plan`` (include/satrl_ppo.h)."""
     _fields_ = ([(k, C.c_int) for k in ("step", "rowpass", "rows_per_block", "row_blocks", "splits", "error_word")] +
@@ -137,6 +144,14 @@ _SIGS = {
     "satenv_cpu_set_act_noise": ([_vp, C.POINTER(SatenvActNoise), _vp], C.c_int),
     "satenv_cpu_get_act_noise": ([_vp, C.POINTER(SatenvActNoise)], C.c_int),
     "satenv_cpu_act_noise_host": ([C.POINTER(SatenvActNoise), _i64, _i32, _i32, _i32, _vp, _vp], C.c_int),
+    "satenv_default_obs_noise": ([C.POINTER(SatenvObsNoise)], C.c_int),
+    "satenv_set_obs_noise": ([_vp, C.POINTER(SatenvObsNoise), _vp], C.c_int),
+    "satenv_get_obs_noise": ([_vp, C.POINTER(SatenvObsNoise)], C.c_int),
+    "satenv_obs_noise_host": ([C.POINTER(SatenvObsNoise), _i64, _i32, _i32, _vp, _vp, _vp], C.c_int),
+    "satenv_cpu_default_obs_noise": ([C.POINTER(SatenvObsNoise)], C.c_int),
+    "satenv_cpu_set_obs_noise": ([_vp, C.POINTER(SatenvObsNoise), _vp], C.c_int),
+    "satenv_cpu_get_obs_noise": ([_vp, C.POINTER(SatenvObsNoise)], C.c_int),
+    "satenv_cpu_obs_noise_host": ([C.POINTER(SatenvObsNoise), _i64, _i32, _i32, _vp, _vp, _vp], C.c_int),
     "satenv_cpu_last_error": ([], C.c_char_p),
     "satenv_cpu_create": ([C.POINTER(_vp), _i64, C.POINTER(SatenvParams), C.c_int], C.c_int),
     "satenv_cpu_destroy": ([_vp], C.c_int),

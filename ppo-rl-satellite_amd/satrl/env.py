@@ -122,6 +122,60 @@ def act_noise_spec(spec):
     return both, both
 
 
+OBS_NOISE_KEYS = ("bias_pos", "bias_vel", "pos", "vel")
+
+
+def obs_noise_craft(c, who="the craft"):
+    """One tracked craft of an obs_noise spec -> its half-widths (bias_pos,
+    bias_vel, pos, vel) as floats: a pair (pos, vel) is the error redrawn at
+    every track refresh, a dict names any of bias_pos, bias_vel (held for a
+    whole episode), pos, vel (missing = 0).  Metres and m/s."""
+    if isinstance(c, dict):
+        unknown = set(c) - set(OBS_NOISE_KEYS)
+        if unknown:
+            raise ValueError(f"obs_noise: {who}'s keys are {', '.join(OBS_NOISE_KEYS)}, "
+                             f"got {sorted(map(str, unknown))}")
+        named = {k: c.get(k, 0.0) for k in OBS_NOISE_KEYS}
+    else:
+        try:
+            pos, vel = c
+        except (TypeError, ValueError):
+            raise ValueError(f"obs_noise: {who} is a pair (pos, vel) or a dict, got {c!r}") from None
+        named = {"bias_pos": 0.0, "bias_vel": 0.0, "pos": pos, "vel": vel}
+    out = []
+    for k in OBS_NOISE_KEYS:
+        try:
+            v = float(named[k])
+        except (TypeError, ValueError):
+            raise ValueError(f"obs_noise: {who}'s {k} is a number, got {named[k]!r}") from None
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ValueError(f"obs_noise: {who}'s {k} must be finite and >= 0, got {named[k]!r}")
+        out.append(v)
+    return tuple(out)
+
+
+def obs_noise_spec(spec):
+    """args_param.obs_noise -> (the pursuer's (bias_pos, bias_vel, pos, vel),
+    the evader's, hold), or None for None.  A pair (pos, vel) holds for both
+    tracked craft with hold 1; a dict {"pursuer": c, "evader": c, "hold": h}
+    names the craft it perturbs (the other one is tracked exactly), c as in
+    obs_noise_craft, and the number of steps h >= 1 a redrawn error is held
+    (include/satenv.h satenv_obs_noise)."""
+    if spec is None:
+        return None
+    if isinstance(spec, dict):
+        unknown = set(spec) - {"pursuer", "evader", "hold"}
+        if unknown:
+            raise ValueError(f"obs_noise: keys are 'pursuer', 'evader' and 'hold', got {sorted(map(str, unknown))}")
+        hold = spec.get("hold", 1)
+        if isinstance(hold, bool) or not isinstance(hold, (int, np.integer)) or not 1 <= int(hold) < 2 ** 31:
+            raise ValueError(f"obs_noise: hold is an int >= 1, got {hold!r}")
+        zero = (0.0, 0.0, 0.0, 0.0)
+        return tuple(obs_noise_craft(spec[k], k) if k in spec else zero for k in ("pursuer", "evader")) + (int(hold),)
+    both = obs_noise_craft(spec, "the spec")
+    return both, both, 1
+
+
 def _num_mode(v) -> int:
     if isinstance(v, np.float32):
         return F32
@@ -192,6 +246,7 @@ class VecSatellites:
         self.stats = torch.zeros(4, dtype=torch.float64, device=self.device)
         self.draws = False               # set_reset_dist was called: the handle launches the drawing step kernels
         self.noisy = False               # set_act_noise was called: ... the step kernels with the actuation noise
+        self.measures = False            # set_obs_noise was called: ... and with the tracking errors on the rows
 
     def _fn(self, name):
         return getattr(_lib.lib(), self._api + name)
@@ -394,6 +449,54 @@ class VecSatellites:
         return {"pursuer": (d.mag[0], d.dir[0]), "evader": (d.mag[1], d.dir[1]), "seed": int(d.seed),
                 "env_offset": int(d.env_offset)}
 
+    # -- tracking errors on the observations (include/satenv.h satenv_obs_noise) --
+    def _get_obs_noise(self):
+        d = _lib.SatenvObsNoise()
+        check(self._fn("get_obs_noise")(self._h, C.byref(d)), self._api + "get_obs_noise")
+        return d
+
+    def _set_obs_noise(self, d):
+        check(self._fn("set_obs_noise")(self._h, C.byref(d), self._sp()), self._api + "set_obs_noise")
+
+    def set_obs_noise(self, pursuer=(0.0, 0.0), evader=(0.0, 0.0), hold: int = 1, seed=0, env_offset: int = 0):
+        """From now on every f32 observation row the env writes (step,
+        step_autoreset, reset) is write_obs of the MEASURED kinematics: each
+        scalar of tracked craft pursuer / evader off by a bias held for the
+        whole episode plus an error redrawn every `hold` steps, bounded
+        uniforms of the half-widths given per craft as (pos, vel) or as a dict
+        with keys among bias_pos, bias_vel, pos, vel (obs_noise_craft) -- a
+        function of (seed, env_offset + i, the env's episode index, the step
+        count) alone.  Both agents read the same row.  The state, rewards,
+        dones, stats and obs64_out stay the truth.  Stream-ordered: graphs
+        captured earlier see it on their next replay -- except graphs captured
+        before this handle's first set_obs_noise (`measures` still False),
+        which hold the kernels without the measurement and must be captured
+        again."""
+        d = _lib.SatenvObsNoise()
+        for g, c in enumerate((pursuer, evader)):
+            d.bias_pos[g], d.bias_vel[g], d.pos[g], d.vel[g] = obs_noise_craft(c, ("pursuer", "evader")[g])
+        d.hold = int(hold)
+        d.seed, d.env_offset, d.enabled = int(seed) & (2 ** 64 - 1), int(env_offset), 1
+        self._set_obs_noise(d)
+        self.measures = True
+
+    def clear_obs_noise(self):
+        """Back to exact observations."""
+        d = self._get_obs_noise()
+        d.enabled = 0
+        self._set_obs_noise(d)
+
+    def obs_noise(self):
+        """None while observations are exact, else a dict: pursuer, evader (each
+        a dict of bias_pos, bias_vel, pos, vel), hold, seed, env_offset."""
+        d = self._get_obs_noise()
+        if not d.enabled:
+            return None
+        craft = [{"bias_pos": d.bias_pos[g], "bias_vel": d.bias_vel[g], "pos": d.pos[g], "vel": d.vel[g]}
+                 for g in (0, 1)]
+        return {"pursuer": craft[0], "evader": craft[1], "hold": int(d.hold), "seed": int(d.seed),
+                "env_offset": int(d.env_offset)}
+
     def episode_index(self):
         """int32 [N]: how many resets each env has had (0 at construction)."""
         out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
@@ -423,8 +526,9 @@ class VecSatellites:
     def full_state(self):
         """Everything a handle carries from one step to the next, as CPU numpy
         arrays: the 15 f64 and 3 i32 planes of get_state, the running episode
-        returns, the episode indices and `stats`.  The reset distribution and
-        the actuation noise are configuration and are not part of it."""
+        returns, the episode indices and `stats`.  The reset distribution, the
+        actuation noise and the observation noise are configuration and are
+        not part of it."""
         f, i = self.get_state()
         return {"f64": f.cpu().numpy(), "i32": i.cpu().numpy(), "ep_return": self.episode_return().cpu().numpy(),
                 "episode_index": self.episode_index().cpu().numpy(), "stats": self.stats.cpu().numpy().copy()}

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import norm as _norm
-from .env import VecSatellites, _typed, act_noise_spec
+from .env import OBS_NOISE_KEYS, VecSatellites, _typed, act_noise_spec, obs_noise_spec
 from .ppo import REC_F64, REC_I32, episode_record, episode_record_reset, policy_eval, policy_eval_scripted
 from .scripted import ScriptedLaw
 
@@ -127,7 +127,8 @@ class VecEvaluator:
     (default: the trainer's N) with the trainer's env parameters.  ``seed``
     keys the sampling agents' noise (default args.seed ^ EVAL_SEED_XOR) and,
     where the trainer's env draws randomised starts, the evaluator's draws
-    from the same box; likewise the actuation noise (evaluate(act_noise=...))."""
+    from the same box; likewise the actuation noise (evaluate(act_noise=...))
+    and the observation noise (evaluate(obs_noise=...))."""
 
     MAX_GRAPHS = 16
 
@@ -231,8 +232,15 @@ class VecEvaluator:
 
     # -- one evaluation -------------------------------------------------------------------
     def evaluate(self, deterministic="learner", max_steps=None, states=None, seed=None, record=False, opponent=None,
-                 act_noise="inherit"):
+                 act_noise="inherit", obs_noise="inherit"):
         tr = self.trainer
+        if isinstance(obs_noise, str):
+            if obs_noise != "inherit":
+                raise ValueError(f"obs_noise is 'inherit', None or a spec (args_param obs_noise), got {obs_noise!r}")
+            now = tr.env.obs_noise()             # the trainer's half-widths and hold as they are now
+            track = None if now is None else obs_noise_spec({k: now[k] for k in ("pursuer", "evader", "hold")})
+        else:
+            track = obs_noise_spec(obs_noise)
         if isinstance(act_noise, str):
             if act_noise != "inherit":
                 raise ValueError(f"act_noise is 'inherit', None or a spec (args_param act_noise), got {act_noise!r}")
@@ -275,6 +283,15 @@ class VecEvaluator:
                     self._graphs.clear()
                     self._laws.clear()
                 env.set_act_noise(noise[0], noise[1], seed, env_offset=tr.env_offset)
+            # ... and the observation noise, before the reset below writes the first row
+            if track is None:
+                env.clear_obs_noise()
+            else:
+                if not env.measures:             # likewise: its graphs hold the step kernel without the measurement
+                    self._graphs.clear()
+                    self._laws.clear()
+                env.set_obs_noise(*(dict(zip(OBS_NOISE_KEYS, c)) for c in track[:2]), hold=track[2], seed=seed,
+                                  env_offset=tr.env_offset)
             env.set_episode_index(None)
             if states is None:
                 env.set_state(*self._state0)

@@ -43,7 +43,7 @@ from . import norm as _norm
 from . import pool as _pool
 from . import scripted as _scripted
 from .buffer import ReplayBuffer, RolloutBuffer
-from .env import VecSatellites, act_noise_spec
+from .env import OBS_NOISE_KEYS, VecSatellites, act_noise_spec, obs_noise_spec
 from .ppo import (PPO_continuous, PPOLearner, gae, gaussian_sample, moments, policy_act, policy_act_league,
                   policy_act_pool, policy_act_scripted, policy_value, reduce_diagnostics_sums)
 
@@ -63,7 +63,7 @@ class args_param:  # noqa: N801
                  diagnostics=False, diagnostics_rows=None, target_kl=None, reset_spread=None, reset_seed=None,
                  opponent_pool=0, opponent_latest_prob=0.5, opponent_snapshot_every=None, opponent_seed=None,
                  scripted_opponent=None, league_laws=None, league_law_prob=0.25, opponent_weighting="uniform",
-                 pfsp_power=2, act_noise=None, act_noise_seed=None):
+                 pfsp_power=2, act_noise=None, act_noise_seed=None, obs_noise=None, obs_noise_seed=None):
         self.max_train_steps = max_train_steps
         self.evaluate_freq = evaluate_freq
         self.save_freq = save_freq
@@ -162,6 +162,19 @@ class args_param:  # noqa: N801
         act_noise_spec(act_noise)                                        # (raises on a malformed spec)
         self.act_noise = act_noise
         self.act_noise_seed = act_noise_seed
+        # observation noise of the vectorised engine (include/satenv.h satenv_obs_noise,
+        # DESIGN.md 3.1.3): None = both agents observe the exact state; (pos, vel) for both
+        # tracked craft, or {"pursuer": c, "evader": c, "hold": h} with every key optional,
+        # c = (pos, vel) or a dict with keys among bias_pos, bias_vel, pos, vel.  Every f32
+        # observation row the env writes is then the row of the measured kinematics: each
+        # scalar of a tracked craft off by a bias in +-bias_* held for the episode plus an
+        # error in +-pos / +-vel redrawn every h steps, keyed by (obs_noise_seed, global env
+        # id, the env's episode index, the step count); obs_noise_seed None = seed.  The
+        # buffer, obs_norm, scripted laws and frozen opponents all read that one row;
+        # rewards, dones and the env's state stay the truth
+        obs_noise_spec(obs_noise)                                        # (raises on a malformed spec)
+        self.obs_noise = obs_noise
+        self.obs_noise_seed = obs_noise_seed
         # opponent pool of the vectorised engine's self-play (satrl/pool.py): per agent
         # a ring of opponent_pool stored parameter sets (0: off, nothing is allocated
         # and the rollout makes the calls it makes without it).  In every iteration
@@ -459,6 +472,9 @@ class VecTrainer:
         ans = getattr(args, "act_noise_seed", None)
         self.act_noise_seed = self.seed if ans is None else int(ans)
         self.set_act_noise(getattr(args, "act_noise", None))
+        ons = getattr(args, "obs_noise_seed", None)
+        self.obs_noise_seed = self.seed if ons is None else int(ons)
+        self.set_obs_noise(getattr(args, "obs_noise", None))
         self._reset_obs()
         if self.obs_norm and int(getattr(args, "obs_norm_calib_steps", 64)) > 0:
             self._calibrate_obs_norm(int(args.obs_norm_calib_steps))
@@ -747,6 +763,28 @@ class VecTrainer:
             return
         was = self.env.noisy
         self.env.set_act_noise(pair[0], pair[1], self.act_noise_seed, env_offset=self.env_offset)
+        if not was:
+            self._graphs.clear()
+
+    def set_obs_noise(self, spec, seed=None):
+        """The env's observation noise (args_param obs_noise; None: exact
+        observations), keyed by `seed` (default: the current noise seed) and
+        this rank's env_offset, so data-parallel shards draw by global env id.
+        It holds from the next observation the env writes on (buf.obs[0], the
+        row in flight, stays as it was written); the captured rollout graphs
+        are replayed as they are.  (Only the first spec of a trainer built
+        without one drops them: they hold the step kernel without the
+        measurement, VecSatellites.set_obs_noise.)"""
+        if seed is not None:
+            self.obs_noise_seed = int(seed)
+        norm = obs_noise_spec(spec)
+        self.obs_noise = spec
+        if norm is None:
+            self.env.clear_obs_noise()
+            return
+        was = self.env.measures
+        self.env.set_obs_noise(*(dict(zip(OBS_NOISE_KEYS, c)) for c in norm[:2]), hold=norm[2],
+                               seed=self.obs_noise_seed, env_offset=self.env_offset)
         if not was:
             self._graphs.clear()
 
@@ -1149,6 +1187,9 @@ class VecTrainer:
         pair = act_noise_spec(self.act_noise)    # (optional likewise) the draw itself needs no state: it is a
         if pair is not None:                     # function of the env id, episode index and step count above
             d["act_noise"] = [list(pair[0]), list(pair[1]), int(self.act_noise_seed)]
+        norm = obs_noise_spec(self.obs_noise)    # (optional too) a row is a function of the same restored values
+        if norm is not None:
+            d["obs_noise"] = [list(norm[0]), list(norm[1]), int(norm[2]), int(self.obs_noise_seed)]
         if self.pools is not None:
             d["league"] = {"law_prob": float(self.league_law_prob), "weighting": self.opponent_weighting,
                            "power": int(self.pfsp_power),
@@ -1221,6 +1262,13 @@ class VecTrainer:
             self.set_act_noise(None)
         else:
             self.set_act_noise({"pursuer": noise[0], "evader": noise[1]}, seed=int(noise[2]))
+        noise = d.get("obs_noise")               # likewise; obs0 / obs_raw above are the saved rows, and the
+        if noise is None:                        # next row the env writes is measured under the saved spec
+            self.set_obs_noise(None)
+        else:
+            self.set_obs_noise({"pursuer": dict(zip(OBS_NOISE_KEYS, noise[0])),
+                                "evader": dict(zip(OBS_NOISE_KEYS, noise[1])),
+                                "hold": int(noise[2])}, seed=int(noise[3]))
         if "gen" in d:
             self.gen.set_state(torch.from_numpy(np.ascontiguousarray(d["gen"], dtype=np.uint8)))
         else:
@@ -1333,7 +1381,7 @@ class VecTrainer:
 
     # -- evaluation (satrl/evaluate.py) -----------------------------------------------------
     def evaluate(self, num_envs=None, deterministic="learner", max_steps=None, states=None, seed=None, record=False,
-                 opponent=None, act_noise="inherit"):
+                 opponent=None, act_noise="inherit", obs_noise="inherit"):
         """The current policies on a fresh env handle of the evaluator's own
         (`num_envs` envs, default N, this env's parameters): every env's first
         episode, at most max_steps steps (default max_episode_steps), as an
@@ -1359,7 +1407,11 @@ class VecTrainer:
         default) runs the evaluator's env under this env's actuation noise as
         it is now, keyed by the evaluation seed; None executes every action
         exactly; a spec (args_param act_noise) evaluates under that spec, so
-        a sweep over it is a robustness curve.  No state of the
+        a sweep over it is a robustness curve.  obs_noise: the same three
+        forms for the observation noise (args_param obs_noise); the records
+        (min_dis, final_dis) stay the truth, and with record=True
+        streams["obs"] is the measurement and streams["obs64"] the truth.
+        No state of the
         trainer changes.  Under data parallelism each rank evaluates its own
         envs; results are not reduced across ranks."""
         from .evaluate import VecEvaluator
@@ -1381,7 +1433,8 @@ class VecTrainer:
         if n not in self._evaluators:
             self._evaluators[n] = VecEvaluator(self, n)
         return self._evaluators[n].evaluate(deterministic=deterministic, max_steps=max_steps, states=states, seed=seed,
-                                            record=record, opponent=opponent, act_noise=act_noise)
+                                            record=record, opponent=opponent, act_noise=act_noise,
+                                            obs_noise=obs_noise)
 
     def evaluate_pool(self, **kw):
         """evaluate(opponent=k, **kw) against every filled slot of the frozen
