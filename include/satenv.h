@@ -40,8 +40,16 @@ enum {
     SATENV_ERR_HIP = -2,
     SATENV_ERR_ORBIT_CIRCULAR = -4,  /* calculate_orbital_elements e == 0 (satellite_function.py:251) */
     SATENV_ERR_ORBIT_PARABOLIC = -5, /* 2/r - v^2/mu == 0 (satellite_function.py:253) */
-    SATENV_ERR_STEP_TOO_SMALL = -6,  /* propagator 2: solve_ivp's RK45 stopped (TOO_SMALL_STEP) */
+    SATENV_ERR_STEP_TOO_SMALL = -6,  /* propagator 2: solve_ivp's RK45 stopped (TOO_SMALL_STEP),
+                                      * or a non-finite state (NaN / inf kinematics or executed action) */
 };
+/* The step kernels record -4 / -5 / -6 in the handle's error word: the first
+ * one recorded stays (sticky, never cleared; which lane is first is not
+ * defined) and satenv_check() reports it.  The lane that recorded it still
+ * finishes its step: an orbit error takes the danger-zone count as 0 (the
+ * dangerous_zone plane is written 0 and the reward uses count 0); every other
+ * output of the lane, and every other lane, is what it is without the error.
+ * Flag 2 and terminal steps never compute the count and record no orbit error. */
 
 /* numpy scalar type carried by the reference's fuel attributes; bits plane:
  * [1:0] fuel_c type, [3:2] fuel_t type, [4] velocities are int64 (fresh

@@ -283,7 +283,8 @@ int orc_cw_rk45(const double x0[6], double tb, double y_out[6], int32_t* nfev_ou
         int accepted = 0, rejected = 0;
         double h = 0.0, t_new = t, y_new[6];
         while (!accepted) {
-            if (h_cur < min_step) { *nfev_out = nfev; return -6; }  /* TOO_SMALL_STEP */
+            /* TOO_SMALL_STEP; !(>=) so that a NaN step size (a non-finite state) leaves too */
+            if (!(h_cur >= min_step)) { *nfev_out = nfev; return -6; }
             h = h_cur * 1.0;
             t_new = t + h;
             if (1.0 * (t_new - tb) > 0) t_new = tb;

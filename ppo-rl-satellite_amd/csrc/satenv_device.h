@@ -745,7 +745,16 @@ SATENV_HD int cw_rk45(double (&y)[6], double tb) {
     bool accepted = false, rejected = false;
     double h = 0.0, t_new = t, yn[6];
     while (!accepted) {                                             // _step_impl (rk.py:111-164)
-      if (hc < min_step) return -6;
+      // Written as !(hc >= min_step), not hc < min_step: the same branch for
+      // every ordered pair, and a NaN step size leaves too.  Both loops end
+      // for every input bit pattern: a non-finite y or f makes h_abs NaN (the
+      // ratios above are inf / inf or NaN and min() keeps them), hc inherits
+      // it and this test returns before the first trial.  Once past it hc is
+      // finite and >= min_step; it stays finite (h = t_new - t of finite
+      // times, times a factor clamped to [0.2, 10] whose NaN arms fall to the
+      // clamps), a rejected trial shrinks it by <= 0.9 until this test fires,
+      // and an accepted one moves t forward by >= 10 ulp towards tb.
+      if (!(hc >= min_step)) return -6;
       t_new = t + hc * 1.0;
       if (1.0 * (t_new - tb) > 0) t_new = tb;
       h = t_new - t;

@@ -31,6 +31,24 @@ STATE_F64 = ["Pp0", "Pp1", "Pp2", "Pv0", "Pv1", "Pv2", "Ep0", "Ep1", "Ep2", "Ev0
 STATE_I32 = ["dz", "episode_count", "bits"]
 
 
+ERROR_NAMES = {-4: "SATENV_ERR_ORBIT_CIRCULAR", -5: "SATENV_ERR_ORBIT_PARABOLIC", -6: "SATENV_ERR_STEP_TOO_SMALL"}
+
+
+class EnvError(RuntimeError):
+    """A step recorded a device error code (include/satenv.h): an env's orbit
+    had no 6-element set (-4 circular, -5 parabolic: the reference crashes
+    there) or propagator 2's RK45 stopped (-6: step too small, or a non-finite
+    state).  `code` is what VecSatellites.check_errors() returned; the word is
+    sticky, so the handle keeps reporting it."""
+
+    def __init__(self, code, where=""):
+        self.code = int(code)
+        name = ERROR_NAMES.get(self.code, "unknown code")
+        super().__init__(f"{where + ': ' if where else ''}the env step recorded error {self.code} ({name}); the "
+                         "lane took a danger-zone count of 0 (-4 / -5) or kept its state unpropagated (-6), so "
+                         "what was collected since the last check is not the reference's")
+
+
 def default_params(**overrides) -> _lib.SatenvParams:
     p = _lib.SatenvParams()
     check(_lib.lib().satenv_default_params(C.byref(p)), "satenv_default_params")

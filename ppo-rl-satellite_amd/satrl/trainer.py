@@ -43,7 +43,7 @@ from . import norm as _norm
 from . import pool as _pool
 from . import scripted as _scripted
 from .buffer import ReplayBuffer, RolloutBuffer
-from .env import OBS_NOISE_KEYS, VecSatellites, act_noise_spec, obs_noise_spec
+from .env import OBS_NOISE_KEYS, EnvError, VecSatellites, act_noise_spec, obs_noise_spec
 from .ppo import (PPO_continuous, PPOLearner, gae, gaussian_sample, moments, policy_act, policy_act_league,
                   policy_act_pool, policy_act_scripted, policy_value, reduce_diagnostics_sums)
 
@@ -1140,6 +1140,9 @@ class VecTrainer:
             self.buf.obs[0].copy_(self.buf.obs[self.T])
         st = _dist.sum_(self.env.stats, self.pg)
         self.episodes = float(st[0].item())
+        code = self.env.check_errors()           # the stream is drained by the item() above: one 4-byte read
+        if code != 0:                            # (this rank's envs; the word is sticky, every later call raises too)
+            raise EnvError(code, f"VecTrainer iteration {self.iteration_count}")
         if self.pools is not None and self._tally_pending:
             self._fold_tally()
         self.iteration_count += 1
